@@ -1,9 +1,17 @@
 #!/usr/bin/env python
 """find_direction throughput on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, the result line
+(its roofline / cpu_baseline / parity fields are null).  ``--full`` adds every other leg described below: the
+roofline pass, the CPU baseline with the direction parity against it, and for N > 1 the N-rank self-check.
+``--dump-outputs DIR`` writes what the last timed step returned to its caller as float32 ``DIR/<name>.npy``:
+``direction`` (the [1, 8, 512] direction after the step's SGD update), ``grad`` (the step's direction gradient,
+same shape) and ``loss_parts`` (its [4] clip / identity / landmarks / l2 loss terms).  Weights, S codes and the
+batch picks are seeded, so the same arguments give the same inputs in every run.
 
 With no launcher in the environment (no WORLD_SIZE), ``--gpus N > 1`` starts the N rank processes itself
 (spawn_ranks: fresh processes, before any GPU call here).  Under a launcher, a WORLD_SIZE that differs from
@@ -20,7 +28,7 @@ per step).  value = images/s = 2 x seeds/s (edited + original
 image per seed), seeds counted exactly (the batch picker can draw the short
 last batch of the 129 seeds).
 
-roofline: the dominant kernel family, the synthesis convs (every smc_conv3x3_wino_f32 / smc_conv_gemm_f32 launch
+roofline (--full): the dominant kernel family, the synthesis convs (every smc_conv3x3_wino_f32 / smc_conv_gemm_f32 launch
 from modconv.py: ``wino4_kernel`` / ``wino_kernel`` for the 3x3 'same' convs, ``conv_gemm_lds_kernel`` / ``conv_row_kernel`` /
 ``convt_lds_kernel`` ... for the rest): the MFMA FLOPs of each launch's algorithm (dense MACs x 2 for the direct
 kernels; 16 / 36 multiplies per 2x2 / 4x4 tile and channel pair for Winograd F(2x2) / F(4x4),
@@ -32,7 +40,7 @@ taken by the other stream's kernels), against the fp32 MFMA peak (157.3 TFLOP/s,
 MI355X_MICROARCH.md).  traffic: HBM bytes per launch from the rocprofv3 PMC pass recorded in
 profiles/pmc_traffic.json (null if absent).
 
-cpu_baseline (rank 0, N=1): the test oracle (pure-torch fp32 CPU restatement of the reference loop,
+cpu_baseline (--full; rank 0, N=1): the test oracle (pure-torch fp32 CPU restatement of the reference loop,
 oracle/, pinned to the reference by tests/golden) running the same step at FFHQ-1024, batch 4: 1 warm-up +
 3 timed iterations on the host's CPU share (affinity set capped by the cgroup quota; os.cpu_count() and the
 CPU model are reported beside it).  parity (same run): the GPU path repeats that exact oracle run and
@@ -78,11 +86,16 @@ def parse():
                    help="hip: ViT on the gfx950 kernel library (config 4); torch: PyTorch-ROCm ops (config 2)")
     p.add_argument("--id-impl", default="hip", choices=["hip", "torch"],
                    help="hip: IR-SE50 on the gfx950 kernel library (config 4); torch: PyTorch-ROCm/MIOpen (config 2)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (direction, grad, loss_parts) as float32 DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the roofline pass, the CPU baseline + direction parity, and (N > 1) the N-rank "
+                        "self-check; without it only the headline figure is measured")
     p.add_argument("--cpu-iters", type=int, default=4, help="CPU baseline / parity iterations (first = warm-up)")
     p.add_argument("--cpu-batch", type=int, default=4)
     p.add_argument("--cpu-threads", type=int, default=0, help="0: the host's CPU share (affinity, cgroup quota)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-kernel-timer", action="store_true", help="skip the roofline pass")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity")
+    p.add_argument("--no-kernel-timer", action="store_true", help="with --full: skip the roofline pass")
     p.add_argument("--roofline-steps", type=int, default=2, help="serialised steps timed per launch for the roofline")
     p.add_argument("--no-batch-losses", action="store_true",
                    help="run the original image's loss-network forwards separately (on the side stream)")
@@ -259,6 +272,16 @@ def pmc_traffic():
     return d.get("conv_gemm_bytes_per_launch"), src
 
 
+def dump_outputs(path, finder):
+    """--dump-outputs: what the last timed step handed its caller (DirectionFinder.step's `grad` and `parts`, and the
+    direction it left in finder.delta), as float32 .npy files -- 8212 numbers in all, so nothing is sampled."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"direction": finder.delta, "grad": finder.last["grad"], "loss_parts": finder.last["parts"]}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to("cpu", torch.float32).contiguous().numpy())
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -370,13 +393,15 @@ def main():
     dt = time.perf_counter() - t0
     dt = world.all_max(dt, dev)
     finite = bool(torch.isfinite(finder.delta).all().item())
+    if args.dump_outputs and world.rank == 0:
+        dump_outputs(args.dump_outputs, finder)
 
     # roofline pass: the same step with the original-image branch serialised onto the main stream, so
     # each GEMM launch's HIP-event duration is its own execution time (with the side stream running
     # concurrently the events would also count CU time taken by the other stream's kernels; rocprofv3's
     # kernel trace, profiles/, measures the serialised duration too)
     roofline = None
-    if not args.no_kernel_timer and args.roofline_steps > 0:
+    if args.full and not args.no_kernel_timer and args.roofline_steps > 0:
         timer = _hip.KernelTimer("conv_gemm")
         finder.overlap = False
         _hip.set_timer(timer)
@@ -445,7 +470,7 @@ def main():
                                 f"timed region"}
 
     selfcheck = None
-    if world.world_size > 1:
+    if args.full and world.world_size > 1:
         selfcheck = dist_selfcheck(G, clip, finder.id_loss, world, dev, finder.temp_shapes, args.resolution,
                                    args.batch)
     if world.rank != 0:
@@ -483,7 +508,7 @@ def main():
     }
     if selfcheck is not None:
         out["parity"] = selfcheck
-    if world.world_size == 1 and not args.no_cpu_baseline:
+    if args.full and world.world_size == 1 and not args.no_cpu_baseline:
         threads, info = host_cpus()
         if args.cpu_threads > 0:
             threads = args.cpu_threads

@@ -3,5 +3,5 @@ OUT=gpurun_out/r01_final; mkdir -p $OUT
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 600 --timeout-method thread -p no:cacheprovider > $OUT/pytest_gpu.log 2>&1; rc=$?; tail -2 $OUT/pytest_gpu.log; grep -E "^E  " $OUT/pytest_gpu.log | head; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -5 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 420 python bench.py > $OUT/bench.log 2>&1 || { tail -5 $OUT/bench.log; exit 1; }
+timeout -k 10 420 python bench.py --full > $OUT/bench.log 2>&1 || { tail -5 $OUT/bench.log; exit 1; }
 grep '^{' $OUT/bench.log | cut -c1-300

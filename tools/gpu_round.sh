@@ -18,7 +18,7 @@ if [ "$K" != "none" ]; then
   [ $rc -eq 0 ] || exit 1
 fi
 if [ "$B" = "bench" ]; then
-  timeout -k 10 500 python bench.py --steps 20 --warmup 5 > $OUT/bench.log 2>&1
+  timeout -k 10 500 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.log 2>&1
   rc=$?
   tail -2 $OUT/bench.log
   exit $rc
