@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 4
+#define SMC_ABI_VERSION 5
 
 #define SMC_OK 0
 #define SMC_ERR_INVALID 1     /* bad argument / shape (reference: TORCH_CHECK -> RuntimeError)   */
@@ -149,9 +149,32 @@ int smc_conv_gemm_last_x3(void);
 int64_t smc_conv_gemm_workspace_size(int n, int cin, int cout, int y_h, int y_w, const smc_conv_phase* phases,
                                      int nphases);
 
+/* Route report of the last smc_conv_gemm_f32 / smc_conv_gemm_aux_f32 call of this thread (tests, attribution; no
+ * launch decision reads it).  A route is one kernel instantiation of the dispatcher, numbered 1 ..
+ * smc_conv_gemm_route_count() - 1 and named by its kernel template and parameters (smc_conv_gemm_route_name; NULL
+ * outside the range); 0 ("none") when the call failed before its launch.  The flags are the modifiers of that
+ * launch: */
+#define SMC_ROUTE_SPLIT_K 1     /* split-K partial planes, summed by the epilogue pass                  */
+#define SMC_ROUTE_PER_SAMPLE 2  /* tiles restarted per image (style-scaled input, straddling tiles)      */
+#define SMC_ROUTE_PRESCALE 4    /* x * s written to the workspace, shared weights                        */
+#define SMC_ROUTE_WSAMPLE 8     /* per-sample weights W * s built in the workspace                       */
+int smc_conv_gemm_last_route(void);
+int smc_conv_gemm_last_route_flags(void);
+int smc_conv_gemm_route_count(void);
+const char* smc_conv_gemm_route_name(int route);
+
 int smc_conv_gemm_f32(const float* x, int n, int cin, int in_h, int in_w, float* y, int cout, int y_h, int y_w,
                       const smc_conv_phase* phases, int nphases, const float* s_in, const smc_conv_epilogue* epi,
                       float* workspace, int64_t workspace_bytes, void* stream);
+
+/* The IR-SE50 executor's planning (its own split-K target and its TAG-1 kernel instantiations), exported so its
+ * instantiations can be verified directly: same arguments and semantics as smc_conv_gemm_workspace_size /
+ * smc_conv_gemm_f32. */
+int64_t smc_conv_gemm_aux_workspace_size(int n, int cin, int cout, int y_h, int y_w, const smc_conv_phase* phases,
+                                         int nphases);
+int smc_conv_gemm_aux_f32(const float* x, int n, int cin, int in_h, int in_w, float* y, int cout, int y_h, int y_w,
+                          const smc_conv_phase* phases, int nphases, const float* s_in, const smc_conv_epilogue* epi,
+                          float* workspace, int64_t workspace_bytes, void* stream);
 
 /* Winograd F(2x2, 3x3) form of the 3x3 stride-1 pad-1 convolution (the SynthesisLayer conv1 forward and its
  * data gradient -- the one-phase smc_conv_gemm_f32 call with taps (dy, dx) in {-1,0,1}^2), same operands and

@@ -19,6 +19,7 @@ c_int, c_int64, c_float, c_void_p, c_char_p = ctypes.c_int, ctypes.c_int64, ctyp
 ACT_CODES = {"linear": 1, "relu": 2, "lrelu": 3, "tanh": 4, "sigmoid": 5, "elu": 6, "selu": 7, "softplus": 8,
              "swish": 9}
 EPI_STORE, EPI_MODACT, EPI_PRELU, EPI_PRELU_GRAD, EPI_AFFINE = 0, 1, 2, 3, 4
+ROUTE_SPLIT_K, ROUTE_PER_SAMPLE, ROUTE_PRESCALE, ROUTE_WSAMPLE = 1, 2, 4, 8
 
 
 class ConvPhase(ctypes.Structure):
@@ -52,6 +53,10 @@ _SIGS = {
     "smc_abi_version": (c_int, []),
     "smc_set_plan_batch": (c_int, [c_int, c_int]),
     "smc_conv_gemm_last_x3": (c_int, []),
+    "smc_conv_gemm_last_route": (c_int, []),
+    "smc_conv_gemm_last_route_flags": (c_int, []),
+    "smc_conv_gemm_route_count": (c_int, []),
+    "smc_conv_gemm_route_name": (c_char_p, [c_int]),
     "smc_last_error": (c_char_p, []),
     "smc_bias_act_f32": (c_int, [P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, c_float, c_float, c_float,
                                  P]),
@@ -59,6 +64,9 @@ _SIGS = {
     "smc_conv_gemm_workspace_size": (c_int64, [c_int, c_int, c_int, c_int, c_int, P, c_int]),
     "smc_conv_gemm_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, c_int, P, P, P, c_int64,
                                   P]),
+    "smc_conv_gemm_aux_workspace_size": (c_int64, [c_int, c_int, c_int, c_int, c_int, P, c_int]),
+    "smc_conv_gemm_aux_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, c_int, P, P, P,
+                                      c_int64, P]),
     "smc_conv_weights_x3_bytes": (c_int64, [c_int, c_int, c_int]),
     "smc_conv_weights_x3": (c_int, [P, c_int, c_int, c_int, P, P]),
     "smc_conv3x3_wino_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
@@ -141,7 +149,7 @@ def load(path=None):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        if lib.smc_abi_version() != 4:
+        if lib.smc_abi_version() != 5:
             raise RuntimeError("stylemc_amd: ABI version mismatch, rebuild the library")
         if path is None:
             _lib = lib

@@ -2038,10 +2038,88 @@ namespace {
 // whether the last conv_gemm_impl call of this thread launched split-bf16 products (smc_conv_gemm_last_x3)
 thread_local int g_last_x3 = 0;
 
+// Route report (smc_conv_gemm_last_route): one value per kernel instantiation conv_gemm_impl launches, the kernel
+// template and its parameters being the identity (NST: the SMC_X3_NST ring depth).  A record only: no launch
+// decision reads it.
+#define SMC_ROUTES(X)                                                   \
+    X(R_CONVT_X3_1421, "convt_x3_kernel<1,4,2,1>")                      \
+    X(R_CONVT_X3_2212, "convt_x3_kernel<2,2,1,2>")                      \
+    X(R_CONVT_X3_1411, "convt_x3_kernel<1,4,1,1>")                      \
+    X(R_CONVT_LDS_2212, "convt_lds_kernel<2,2,1,2,16>")                 \
+    X(R_CONVT_LDS_1411, "convt_lds_kernel<1,4,1,1,16>")                 \
+    X(R_CONVT_GEMM_2221, "convt_gemm_kernel<2,2,2,1,16>")               \
+    X(R_CONVT_GEMM_1421, "convt_gemm_kernel<1,4,2,1,16>")               \
+    X(R_CONVT_GEMM_1411, "convt_gemm_kernel<1,4,1,1,16>")               \
+    X(R_CONVT_GEMM_1412, "convt_gemm_kernel<1,4,1,2,16>")               \
+    X(R_X3_WIDE, "conv_gemm_x3_kernel<1,4,8,1,16,2,0,true>")            \
+    X(R_X3_1441_16, "conv_gemm_x3_kernel<1,4,4,1,16>")                  \
+    X(R_X3_1421_16, "conv_gemm_x3_kernel<1,4,2,1,16>")                  \
+    X(R_X3_1441_32, "conv_gemm_x3_kernel<1,4,4,1,32>")                  \
+    X(R_X3_1421_32, "conv_gemm_x3_kernel<1,4,2,1,32>")                  \
+    X(R_X3_2222_32_T1, "conv_gemm_x3_kernel<2,2,2,2,32,NST,1>")         \
+    X(R_X3_2222_32, "conv_gemm_x3_kernel<2,2,2,2,32>")                  \
+    X(R_X3_2222_16_T1, "conv_gemm_x3_kernel<2,2,2,2,16,NST,1>")         \
+    X(R_X3_2222_16, "conv_gemm_x3_kernel<2,2,2,2,16>")                  \
+    X(R_X3_2211_32_T1, "conv_gemm_x3_kernel<2,2,1,1,32,NST,1>")         \
+    X(R_X3_2211_16_T1, "conv_gemm_x3_kernel<2,2,1,1,16,NST,1>")         \
+    X(R_X3_2211_32, "conv_gemm_x3_kernel<2,2,1,1,32>")                  \
+    X(R_X3_2211_16, "conv_gemm_x3_kernel<2,2,1,1,16>")                  \
+    X(R_X3_1411_32, "conv_gemm_x3_kernel<1,4,1,1,32>")                  \
+    X(R_X3_1411_16, "conv_gemm_x3_kernel<1,4,1,1,16>")                  \
+    X(R_X3_2212_32, "conv_gemm_x3_kernel<2,2,1,2,32>")                  \
+    X(R_X3_2212_16, "conv_gemm_x3_kernel<2,2,1,2,16>")                  \
+    X(R_ROW_1412, "conv_row_kernel<1,4,1,2,8>")                         \
+    X(R_ROW_1422, "conv_row_kernel<1,4,2,2,8>")                         \
+    X(R_LDS_2222_32_T1, "conv_gemm_lds_kernel<2,2,2,2,32,2,1>")         \
+    X(R_LDS_2222_32, "conv_gemm_lds_kernel<2,2,2,2,32,2>")              \
+    X(R_LDS_2222_16_T1, "conv_gemm_lds_kernel<2,2,2,2,16,2,1>")         \
+    X(R_LDS_2222_16, "conv_gemm_lds_kernel<2,2,2,2,16,2>")              \
+    X(R_LDS_2211_32_T1, "conv_gemm_lds_kernel<2,2,1,1,32,2,1>")         \
+    X(R_LDS_2211_16_T1, "conv_gemm_lds_kernel<2,2,1,1,16,2,1>")         \
+    X(R_LDS_2211_16, "conv_gemm_lds_kernel<2,2,1,1,16,2>")              \
+    X(R_LDS_1411_16_T1, "conv_gemm_lds_kernel<1,4,1,1,16,2,1>")         \
+    X(R_LDS_1411_16, "conv_gemm_lds_kernel<1,4,1,1,16,2>")              \
+    X(R_LDS_2212_16_T1, "conv_gemm_lds_kernel<2,2,1,2,16,2,1>")         \
+    X(R_LDS_2212_16, "conv_gemm_lds_kernel<2,2,1,2,16,2>")              \
+    SMC_ROUTES_REG(X, 2222, "2,2,2,2")                                  \
+    SMC_ROUTES_REG(X, 1411, "1,4,1,1")                                  \
+    SMC_ROUTES_REG(X, 2212, "2,2,1,2")                                  \
+    SMC_ROUTES_REG(X, 2211, "2,2,1,1")
+// the register-staged kernel's six forms per tile: BK 32 / 16, buffer loads (input < 2 GiB) or 64-bit addressing, TAG
+#define SMC_ROUTES_REG(X, T, S)                                         \
+    X(R_REG_##T##_32_BUF_T1, "conv_gemm_kernel<" S ",32,true,1>")       \
+    X(R_REG_##T##_16_BUF_T1, "conv_gemm_kernel<" S ",16,true,1>")       \
+    X(R_REG_##T##_32_BUF, "conv_gemm_kernel<" S ",32,true>")            \
+    X(R_REG_##T##_32, "conv_gemm_kernel<" S ",32,false>")               \
+    X(R_REG_##T##_16_BUF, "conv_gemm_kernel<" S ",16,true>")            \
+    X(R_REG_##T##_16, "conv_gemm_kernel<" S ",16,false>")
+
+enum Route {
+    R_NONE = 0,
+#define SMC_ROUTE_ENUM(id, name) id,
+    SMC_ROUTES(SMC_ROUTE_ENUM)
+#undef SMC_ROUTE_ENUM
+    kRouteCount
+};
+
+constexpr const char* kRouteNames[] = {
+    "none",
+#define SMC_ROUTE_NAME(id, name) name,
+    SMC_ROUTES(SMC_ROUTE_NAME)
+#undef SMC_ROUTE_NAME
+};
+static_assert(sizeof(kRouteNames) / sizeof(kRouteNames[0]) == kRouteCount, "one name per route");
+static_assert(R_REG_2211_16 == kRouteCount - 1, "the route list and the enum agree");
+
+thread_local int g_last_route = R_NONE;
+thread_local int g_last_flags = 0;  // SMC_ROUTE_* modifiers of that launch (smc_conv_gemm_last_route_flags)
+
 int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y, int cout, int y_h, int y_w,
                    const smc_conv_phase* phases, int nphases, const float* s_in, const smc_conv_epilogue* epi,
                    float* workspace, int64_t workspace_bytes, void* stream, int tag) {
     g_last_x3 = 0;
+    g_last_route = R_NONE;
+    g_last_flags = 0;
     int rc = validate(x, n, cin, in_h, in_w, y, cout, y_h, y_w, phases, nphases);
     if (rc != SMC_OK) return rc;
     Cfg c;
@@ -2080,7 +2158,9 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
         SMC_CHECK(workspace && workspace_bytes >= need, "smc_conv_gemm_f32: workspace %lld < %lld bytes",
                   (long long)workspace_bytes, (long long)need);
     }
+    if (nsplit > 1) g_last_flags |= SMC_ROUTE_SPLIT_K;
     if (prescale) {
+        g_last_flags |= SMC_ROUTE_PRESCALE;
         // x * s after the split-K partials (the query reserved max(per-sample weights, prescaled input))
         const int64_t part = nsplit > 1 ? ((nsplit * plane_elems * (int64_t)sizeof(float) + 255) / 256) * 256 : 0;
         const int64_t need = part + pre_fl * (int64_t)sizeof(float);
@@ -2134,6 +2214,7 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
     hipStream_t st = smc::as_stream(stream);
     // per-sample weights W[t][i][o] * s[n][i], [phase][n][taps*cin][cout], after the split-K partials
     auto make_wsample = [&]() -> int {
+        g_last_flags |= SMC_ROUTE_WSAMPLE;
         const int64_t part = nsplit > 1 ? ((nsplit * plane_elems * (int64_t)sizeof(float) + 255) / 256) * 256 : 0;
         const int64_t need = part + wsample_floats(n, cin, cout, phases, nphases) * (int64_t)sizeof(float);
         SMC_CHECK(workspace && workspace_bytes >= need, "smc_conv_gemm_f32: workspace %lld < %lld bytes",
@@ -2173,14 +2254,15 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
         const int64_t hw_g = (int64_t)(in_h + 1) * (in_w + 1);
         const int64_t mt = t_per_sample ? n * smc::ceil_div(hw_g, tl.bm) : smc::ceil_div(n * hw_g, tl.bm);
         p.per_sample = t_per_sample ? 1 : 0;
+        if (t_per_sample) g_last_flags |= SMC_ROUTE_PER_SAMPLE;
         p.ntn = cout / tl.bo;
         dim3 g((unsigned)(mt * p.ntn), 1, (unsigned)nsplit);
         g_last_x3 = x3 ? 1 : 0;
-        if (x3 && tl.id == 1 && SMC_X3_WO1) hipLaunchKernelGGL((convt_x3_kernel<1, 4, 2, 1>), g, dim3(NT), 0, st, p, ctt);
-        else if (x3 && tl.id == 1) hipLaunchKernelGGL((convt_x3_kernel<2, 2, 1, 2>), g, dim3(NT), 0, st, p, ctt);
-        else if (x3) hipLaunchKernelGGL((convt_x3_kernel<1, 4, 1, 1>), g, dim3(NT), 0, st, p, ctt);
-        else if (tl.id == 1) hipLaunchKernelGGL((convt_lds_kernel<2, 2, 1, 2, 16>), g, dim3(NT), 0, st, p, ctt);
-        else hipLaunchKernelGGL((convt_lds_kernel<1, 4, 1, 1, 16>), g, dim3(NT), 0, st, p, ctt);
+        if (x3 && tl.id == 1 && SMC_X3_WO1) { g_last_route = R_CONVT_X3_1421; hipLaunchKernelGGL((convt_x3_kernel<1, 4, 2, 1>), g, dim3(NT), 0, st, p, ctt); }
+        else if (x3 && tl.id == 1) { g_last_route = R_CONVT_X3_2212; hipLaunchKernelGGL((convt_x3_kernel<2, 2, 1, 2>), g, dim3(NT), 0, st, p, ctt); }
+        else if (x3) { g_last_route = R_CONVT_X3_1411; hipLaunchKernelGGL((convt_x3_kernel<1, 4, 1, 1>), g, dim3(NT), 0, st, p, ctt); }
+        else if (tl.id == 1) { g_last_route = R_CONVT_LDS_2212; hipLaunchKernelGGL((convt_lds_kernel<2, 2, 1, 2, 16>), g, dim3(NT), 0, st, p, ctt); }
+        else { g_last_route = R_CONVT_LDS_1411; hipLaunchKernelGGL((convt_lds_kernel<1, 4, 1, 1, 16>), g, dim3(NT), 0, st, p, ctt); }
         rc = smc::check_launch("smc_conv_gemm_f32 (fused transposed conv, LDS-DMA)");
         if (rc != SMC_OK || nsplit == 1) return rc;
         return smc_modconv_epilogue_f32(workspace, nsplit, plane_elems, y, n, cout, y_h, y_w, &e, stream);
@@ -2189,10 +2271,10 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
         const ConvTCfg tc = convt_cfg(cout);
         const int64_t M = (int64_t)n * (in_h + 1) * (in_w + 1);
         dim3 g((unsigned)smc::ceil_div(M, tc.bm), (unsigned)smc::ceil_div(cout, tc.bo), (unsigned)nsplit);
-        if (tc.id == 0) hipLaunchKernelGGL((convt_gemm_kernel<2, 2, 2, 1, 16>), g, dim3(NT), 0, st, p, ctp);
-        else if (tc.id == 1) hipLaunchKernelGGL((convt_gemm_kernel<1, 4, 2, 1, 16>), g, dim3(NT), 0, st, p, ctp);
-        else if (tc.id == 3) hipLaunchKernelGGL((convt_gemm_kernel<1, 4, 1, 1, 16>), g, dim3(NT), 0, st, p, ctp);
-        else hipLaunchKernelGGL((convt_gemm_kernel<1, 4, 1, 2, 16>), g, dim3(NT), 0, st, p, ctp);
+        if (tc.id == 0) { g_last_route = R_CONVT_GEMM_2221; hipLaunchKernelGGL((convt_gemm_kernel<2, 2, 2, 1, 16>), g, dim3(NT), 0, st, p, ctp); }
+        else if (tc.id == 1) { g_last_route = R_CONVT_GEMM_1421; hipLaunchKernelGGL((convt_gemm_kernel<1, 4, 2, 1, 16>), g, dim3(NT), 0, st, p, ctp); }
+        else if (tc.id == 3) { g_last_route = R_CONVT_GEMM_1411; hipLaunchKernelGGL((convt_gemm_kernel<1, 4, 1, 1, 16>), g, dim3(NT), 0, st, p, ctp); }
+        else { g_last_route = R_CONVT_GEMM_1412; hipLaunchKernelGGL((convt_gemm_kernel<1, 4, 1, 2, 16>), g, dim3(NT), 0, st, p, ctp); }
         rc = smc::check_launch("smc_conv_gemm_f32 (fused transposed conv)");
         if (rc != SMC_OK || nsplit == 1) return rc;
         return smc_modconv_epilogue_f32(workspace, nsplit, plane_elems, y, n, cout, y_h, y_w, &e, stream);
@@ -2213,6 +2295,7 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
                 tps = std::max<int64_t>(tps, smc::ceil_div((int64_t)phases[i].out_h * phases[i].out_w, c.bm));
             grid.x = (unsigned)(tps * n);
             p.per_sample = 1;
+            g_last_flags |= SMC_ROUTE_PER_SAMPLE;
         }
         if (s_in) {
             rc = make_wsample();
@@ -2231,24 +2314,24 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
             // 32-channel K steps for the narrow tiles too (A/B knob SMC_X3_K32_SMALL: half the barriers per FLOP)
             const bool k32s = SMC_X3_K32_SMALL && cin % 32 == 0;
             g_last_x3 = cfg == 6 ? 2 : 1;
-            if (cfg == 6) hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 8, 1, 16, 2, 0, true>), grid, dim3(NT), 0, st, p);
-            else if (SMC_X3_WO1 && SMC_X3_WO1_K16 && cfg == 0 && !tag) hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 4, 1, 16>), grid, dim3(NT), 0, st, p);
-            else if (SMC_X3_WO1 && SMC_X3_WO1_K16 && cfg == 5 && !tag) hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 2, 1, 16>), grid, dim3(NT), 0, st, p);
-            else if (SMC_X3_WO1 && cfg == 0 && k32 && !tag) hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 4, 1, 32>), grid, dim3(NT), 0, st, p);
-            else if (SMC_X3_WO1 && cfg == 5 && k32s && !tag) hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 2, 1, 32>), grid, dim3(NT), 0, st, p);
-            else if (cfg == 0 && k32 && tag) hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 2, 2, 32, SMC_X3_NST, 1>), grid, dim3(NT), 0, st, p);
-            else if (cfg == 0 && k32) hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 2, 2, 32>), grid, dim3(NT), 0, st, p);
-            else if (cfg == 0 && tag) hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 2, 2, 16, SMC_X3_NST, 1>), grid, dim3(NT), 0, st, p);
-            else if (cfg == 0) hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 2, 2, 16>), grid, dim3(NT), 0, st, p);
+            if (cfg == 6) { g_last_route = R_X3_WIDE; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 8, 1, 16, 2, 0, true>), grid, dim3(NT), 0, st, p); }
+            else if (SMC_X3_WO1 && SMC_X3_WO1_K16 && cfg == 0 && !tag) { g_last_route = R_X3_1441_16; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 4, 1, 16>), grid, dim3(NT), 0, st, p); }
+            else if (SMC_X3_WO1 && SMC_X3_WO1_K16 && cfg == 5 && !tag) { g_last_route = R_X3_1421_16; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 2, 1, 16>), grid, dim3(NT), 0, st, p); }
+            else if (SMC_X3_WO1 && cfg == 0 && k32 && !tag) { g_last_route = R_X3_1441_32; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 4, 1, 32>), grid, dim3(NT), 0, st, p); }
+            else if (SMC_X3_WO1 && cfg == 5 && k32s && !tag) { g_last_route = R_X3_1421_32; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 2, 1, 32>), grid, dim3(NT), 0, st, p); }
+            else if (cfg == 0 && k32 && tag) { g_last_route = R_X3_2222_32_T1; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 2, 2, 32, SMC_X3_NST, 1>), grid, dim3(NT), 0, st, p); }
+            else if (cfg == 0 && k32) { g_last_route = R_X3_2222_32; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 2, 2, 32>), grid, dim3(NT), 0, st, p); }
+            else if (cfg == 0 && tag) { g_last_route = R_X3_2222_16_T1; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 2, 2, 16, SMC_X3_NST, 1>), grid, dim3(NT), 0, st, p); }
+            else if (cfg == 0) { g_last_route = R_X3_2222_16; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 2, 2, 16>), grid, dim3(NT), 0, st, p); }
             else if (cfg == 3 && cin % 32 == 0 && tag)
-                hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 1, 32, SMC_X3_NST, 1>), grid, dim3(NT), 0, st, p);
-            else if (cfg == 3 && tag) hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 1, 16, SMC_X3_NST, 1>), grid, dim3(NT), 0, st, p);
-            else if (cfg == 3 && k32s) hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 1, 32>), grid, dim3(NT), 0, st, p);
-            else if (cfg == 3) hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 1, 16>), grid, dim3(NT), 0, st, p);
-            else if (cfg == 4 && k32s) hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 1, 1, 32>), grid, dim3(NT), 0, st, p);
-            else if (cfg == 4) hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 1, 1, 16>), grid, dim3(NT), 0, st, p);
-            else if (k32s) hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 2, 32>), grid, dim3(NT), 0, st, p);
-            else hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 2, 16>), grid, dim3(NT), 0, st, p);
+                { g_last_route = R_X3_2211_32_T1; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 1, 32, SMC_X3_NST, 1>), grid, dim3(NT), 0, st, p); }
+            else if (cfg == 3 && tag) { g_last_route = R_X3_2211_16_T1; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 1, 16, SMC_X3_NST, 1>), grid, dim3(NT), 0, st, p); }
+            else if (cfg == 3 && k32s) { g_last_route = R_X3_2211_32; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 1, 32>), grid, dim3(NT), 0, st, p); }
+            else if (cfg == 3) { g_last_route = R_X3_2211_16; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 1, 16>), grid, dim3(NT), 0, st, p); }
+            else if (cfg == 4 && k32s) { g_last_route = R_X3_1411_32; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 1, 1, 32>), grid, dim3(NT), 0, st, p); }
+            else if (cfg == 4) { g_last_route = R_X3_1411_16; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 1, 1, 16>), grid, dim3(NT), 0, st, p); }
+            else if (k32s) { g_last_route = R_X3_2212_32; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 2, 32>), grid, dim3(NT), 0, st, p); }
+            else { g_last_route = R_X3_2212_16; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 2, 16>), grid, dim3(NT), 0, st, p); }
             rc = smc::check_launch("smc_conv_gemm_f32 (split-bf16)");
             if (rc != SMC_OK || nsplit == 1) return rc;
             return smc_modconv_epilogue_f32(workspace, nsplit, plane_elems, y, n, cout, y_h, y_w, &e, stream);
@@ -2261,24 +2344,24 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
             // channels, 64 x 256: r = 512 655 / 648 (688 / 679).  128+ channels stay tap-major (the 128 x 128
             // row tile: 690 vs 634 us at r = 256).
             const int tiles = (int)(((int64_t)n * in_h * in_w) / 256) * p.ntn;
-            if (cfg == 4) hipLaunchKernelGGL((conv_row_kernel<1, 4, 1, 2, 8>), dim3(tiles), dim3(NT), 0, st, p, rt);
-            else hipLaunchKernelGGL((conv_row_kernel<1, 4, 2, 2, 8>), dim3(tiles), dim3(NT), 0, st, p, rt);
+            if (cfg == 4) { g_last_route = R_ROW_1412; hipLaunchKernelGGL((conv_row_kernel<1, 4, 1, 2, 8>), dim3(tiles), dim3(NT), 0, st, p, rt); }
+            else { g_last_route = R_ROW_1422; hipLaunchKernelGGL((conv_row_kernel<1, 4, 2, 2, 8>), dim3(tiles), dim3(NT), 0, st, p, rt); }
             return smc::check_launch("smc_conv_gemm_f32 (row-halo)");
         }
 #define SMC_LAUNCH_LDS(WO_, WM_, TO_, TM_)                                                                          \
     do {                                                                                                          \
-        if (tag) hipLaunchKernelGGL((conv_gemm_lds_kernel<WO_, WM_, TO_, TM_, 16, 2, 1>), grid, dim3(NT), 0, st, p); \
-        else hipLaunchKernelGGL((conv_gemm_lds_kernel<WO_, WM_, TO_, TM_, 16, 2>), grid, dim3(NT), 0, st, p);       \
+        if (tag) { g_last_route = R_LDS_##WO_##WM_##TO_##TM_##_16_T1; hipLaunchKernelGGL((conv_gemm_lds_kernel<WO_, WM_, TO_, TM_, 16, 2, 1>), grid, dim3(NT), 0, st, p); } \
+        else { g_last_route = R_LDS_##WO_##WM_##TO_##TM_##_16; hipLaunchKernelGGL((conv_gemm_lds_kernel<WO_, WM_, TO_, TM_, 16, 2>), grid, dim3(NT), 0, st, p); } \
     } while (0)
         if (cfg == 0 && lds_bk32(cfg, cin) && tag)
-            hipLaunchKernelGGL((conv_gemm_lds_kernel<2, 2, 2, 2, 32, 2, 1>), grid, dim3(NT), 0, st, p);
+            { g_last_route = R_LDS_2222_32_T1; hipLaunchKernelGGL((conv_gemm_lds_kernel<2, 2, 2, 2, 32, 2, 1>), grid, dim3(NT), 0, st, p); }
         else if (cfg == 0 && lds_bk32(cfg, cin))
-            hipLaunchKernelGGL((conv_gemm_lds_kernel<2, 2, 2, 2, 32, 2>), grid, dim3(NT), 0, st, p);
+            { g_last_route = R_LDS_2222_32; hipLaunchKernelGGL((conv_gemm_lds_kernel<2, 2, 2, 2, 32, 2>), grid, dim3(NT), 0, st, p); }
         else if (cfg == 0) SMC_LAUNCH_LDS(2, 2, 2, 2);
         // IR-SE50 (TAG 1) 64x64 tiles: 32-channel K steps (half the barriers of a 9-step split):
         // f(4) + b(4) 3.57 -> 3.52 ms (profiles/r03_irse_bk32_ab.txt)
         else if (cfg == 3 && cin % 32 == 0 && tag)
-            hipLaunchKernelGGL((conv_gemm_lds_kernel<2, 2, 1, 1, 32, 2, 1>), grid, dim3(NT), 0, st, p);
+            { g_last_route = R_LDS_2211_32_T1; hipLaunchKernelGGL((conv_gemm_lds_kernel<2, 2, 1, 1, 32, 2, 1>), grid, dim3(NT), 0, st, p); }
         else if (cfg == 3) SMC_LAUNCH_LDS(2, 2, 1, 1);
         else if (cfg == 4) SMC_LAUNCH_LDS(1, 4, 1, 1);
         else SMC_LAUNCH_LDS(2, 2, 1, 2);
@@ -2295,12 +2378,12 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
     const bool buf = (int64_t)n * cin * in_h * in_w * 4 < (1LL << 31);
 #define SMC_LAUNCH(WO_, WM_, TO_, TM_)                                                                       \
     do {                                                                                                   \
-        if (k32 && buf && tag) hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 32, true, 1>), grid, dim3(NT), 0, st, p); \
-        else if (buf && tag) hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 16, true, 1>), grid, dim3(NT), 0, st, p); \
-        else if (k32 && buf) hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 32, true>), grid, dim3(NT), 0, st, p);   \
-        else if (k32) hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 32, false>), grid, dim3(NT), 0, st, p);    \
-        else if (buf) hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 16, true>), grid, dim3(NT), 0, st, p);     \
-        else hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 16, false>), grid, dim3(NT), 0, st, p);             \
+        if (k32 && buf && tag) { g_last_route = R_REG_##WO_##WM_##TO_##TM_##_32_BUF_T1; hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 32, true, 1>), grid, dim3(NT), 0, st, p); } \
+        else if (buf && tag) { g_last_route = R_REG_##WO_##WM_##TO_##TM_##_16_BUF_T1; hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 16, true, 1>), grid, dim3(NT), 0, st, p); } \
+        else if (k32 && buf) { g_last_route = R_REG_##WO_##WM_##TO_##TM_##_32_BUF; hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 32, true>), grid, dim3(NT), 0, st, p); }   \
+        else if (k32) { g_last_route = R_REG_##WO_##WM_##TO_##TM_##_32; hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 32, false>), grid, dim3(NT), 0, st, p); }    \
+        else if (buf) { g_last_route = R_REG_##WO_##WM_##TO_##TM_##_16_BUF; hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 16, true>), grid, dim3(NT), 0, st, p); }     \
+        else { g_last_route = R_REG_##WO_##WM_##TO_##TM_##_16; hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 16, false>), grid, dim3(NT), 0, st, p); }             \
     } while (0)
     if (cfg == 0) SMC_LAUNCH(2, 2, 2, 2);
     else if (cfg == 4) SMC_LAUNCH(1, 4, 1, 1);
@@ -2315,6 +2398,16 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
 }  // namespace
 
 SMC_API int smc_conv_gemm_last_x3(void) { return g_last_x3; }
+
+SMC_API int smc_conv_gemm_last_route(void) { return g_last_route; }
+
+SMC_API int smc_conv_gemm_last_route_flags(void) { return g_last_flags; }
+
+SMC_API int smc_conv_gemm_route_count(void) { return kRouteCount; }
+
+SMC_API const char* smc_conv_gemm_route_name(int route) {
+    return route >= 0 && route < kRouteCount ? kRouteNames[route] : nullptr;
+}
 
 SMC_API int64_t smc_conv_weights_x3_bytes(int ntaps, int cin, int cout) {
     if (ntaps < 1 || ntaps > 9 || cin < 16 || cin % 16 || cout < 1) return 0;
@@ -2353,3 +2446,16 @@ int conv_gemm_aux(const float* x, int n, int cin, int in_h, int in_w, float* y, 
                           workspace_bytes, stream, 1);
 }
 }  // namespace smc
+
+SMC_API int64_t smc_conv_gemm_aux_workspace_size(int n, int cin, int cout, int y_h, int y_w,
+                                                 const smc_conv_phase* phases, int nphases) {
+    return smc::conv_gemm_aux_workspace_size(n, cin, cout, y_h, y_w, phases, nphases);
+}
+
+SMC_API int smc_conv_gemm_aux_f32(const float* x, int n, int cin, int in_h, int in_w, float* y, int cout, int y_h,
+                                  int y_w, const smc_conv_phase* phases, int nphases, const float* s_in,
+                                  const smc_conv_epilogue* epi, float* workspace, int64_t workspace_bytes,
+                                  void* stream) {
+    return smc::conv_gemm_aux(x, n, cin, in_h, in_w, y, cout, y_h, y_w, phases, nphases, s_in, epi, workspace,
+                              workspace_bytes, stream);
+}

@@ -235,6 +235,14 @@ def test_synthesis_layer_grad_subsets():
     close(dxc, dxa, 1e-6, "dx only")
 
 
+def _route():
+    """Name of the kernel instantiation the last direct-conv launch of this thread ran (smc_conv_gemm_route_name of
+    smc_conv_gemm_last_route)."""
+    from stylemc_amd import _hip
+    lib = _hip.load()
+    return lib.smc_conv_gemm_route_name(lib.smc_conv_gemm_last_route()).decode()
+
+
 def _both_forms(monkeypatch, run, what):
     """run() -> [(gpu result, fp64 reference), ...] once with split-bf16 products (modconv.X3) and once with the
     exact-fp32 MFMA.  Exact fp32: within 2e-5 of the max vs fp64 (no activation, so no kinks).  Split-bf16: within
@@ -261,10 +269,11 @@ def _both_forms(monkeypatch, run, what):
                                            (2, 512, 512, 16), (4, 512, 512, 8), (3, 128, 64, 24)])
 def test_conv_gemm_same3x3_vs_conv2d(n, cin, cout, r, monkeypatch):
     """3x3 'same' convs (conv1 forward with per-sample style-scaled weights, and its data gradient with the
-    shared flipped weights) against an fp64 CPU convolution.  Exact-fp32 MFMA: 32 / 64 output channels with
-    W % 256 == 0 run the row-halo kernel (conv_row_kernel, both tile widths), the other shapes the tap-major LDS-DMA
-    kernel; split-bf16: every shape the LDS-DMA tiles with split products (per-sample split weights in the forward,
-    split-K at 8 and 16 px)."""
+    shared flipped weights) against an fp64 CPU convolution.  Exact-fp32 MFMA: 32 / 64 / 96 output channels (the
+    96-channel data gradient as 3 x 32) with W % 256 == 0 run the row-halo kernel (conv_row_kernel, both tile widths;
+    unsplit on 256 CUs), the other shapes the tap-major LDS-DMA kernel; split-bf16: every shape the LDS-DMA tiles with
+    split products (per-sample split weights in the forward, a prescaled input instead at 8 / 16 / 24 px, split-K
+    there too).  Both launches assert the kernel family they ran (smc_conv_gemm_last_route)."""
     import torch.nn.functional as F
     from stylemc_amd import _hip, modconv
     gen = torch.Generator().manual_seed(11)
@@ -280,10 +289,19 @@ def test_conv_gemm_same3x3_vs_conv2d(n, cin, cout, r, monkeypatch):
         ph, nph, _, _ = P.fwd_phases(r, r)
         y = torch.empty(n, cout, r, r, device=DEV)
         modconv.gemm(x.to(DEV), y, ph, nph, cin, cout, s=s.to(DEV), epi=modconv._epilogue(_hip.EPI_STORE))
+        routes = [_route()]
         phb, nphb = P.bwd_phases(r, r)
         dx = torch.empty(n, cin, r, r, device=DEV)
         modconv.gemm(g.to(DEV), dx, phb, nphb, cout, cin, epi=modconv._epilogue(_hip.EPI_STORE))
+        routes.append(_route())
         assert (P.x3_fwd is not None) == form
+        for name, co in zip(routes, (cout, cin)):   # co: the launch's output channels
+            if form:
+                assert name.startswith("conv_gemm_x3_kernel<"), name
+            elif not (r % 256 == 0 and co <= 96):
+                assert name.startswith("conv_gemm_lds_kernel<"), name
+            elif torch.cuda.get_device_properties(0).multi_processor_count == 256:   # unsplit there: the row kernel
+                assert name.startswith("conv_row_kernel<"), name
         return [(y, ref), (dx, refb)]
 
     _both_forms(monkeypatch, run, "3x3 fwd / data grad")
@@ -317,10 +335,11 @@ def test_conv_gemm_stride2_gather_vs_conv2d(n, cin, cout, h, monkeypatch):
 @pytest.mark.parametrize("n,cin,cout,h", [(2, 64, 32, 64), (1, 128, 64, 128), (2, 512, 512, 4), (3, 256, 128, 16),
                                            (1, 512, 256, 32), (2, 32, 32, 33), (4, 512, 512, 8)])
 def test_conv_gemm_transposed_vs_conv_transpose2d(n, cin, cout, h, monkeypatch):
-    """The up = 2 layers' stride-2 transposed 3x3 conv (conv2d_resample.py:125-138 before the blur) as the
-    phase-fused LDS-DMA kernel: per-sample style-scaled weights with tiles restarted per image ((h+1)^2 not a
-    tile multiple), a prescaled input at the low resolutions, split-K over channel chunks; vs fp64
-    conv_transpose2d, both product forms (_both_forms)."""
+    """The up = 2 layers' stride-2 transposed 3x3 conv (conv2d_resample.py:125-138 before the blur): 32 / 64 output
+    channels as the phase-fused LDS-DMA kernel (convt_lds_kernel / convt_x3_kernel), from 128 up as four phases of
+    the tap-major LDS-DMA kernels (asserted, smc_conv_gemm_last_route): per-sample style-scaled weights with tiles
+    restarted per image ((h+1)^2 not a tile multiple), a prescaled input at the low resolutions, split-K over channel
+    chunks; vs fp64 conv_transpose2d, both product forms (_both_forms)."""
     import torch.nn.functional as F
     from stylemc_amd import _hip, modconv
     gen = torch.Generator().manual_seed(13)
@@ -334,6 +353,10 @@ def test_conv_gemm_transposed_vs_conv_transpose2d(n, cin, cout, h, monkeypatch):
         ph, nph, th, tw = P.fwd_phases(h, h)
         t = torch.empty(n, cout, th, tw, device=DEV)
         modconv.gemm(x.to(DEV), t, ph, nph, cin, cout, s=s.to(DEV), epi=modconv._epilogue(_hip.EPI_STORE))
+        fused = cout <= 64
+        assert _route().startswith({(True, True): "convt_x3_kernel<", (True, False): "convt_lds_kernel<",
+                                    (False, True): "conv_gemm_x3_kernel<", (False, False): "conv_gemm_lds_kernel<"}[
+                                        (fused, form)]), _route()
         assert all((w is not None) == form for w in P.x3_phases)
         return [(t, ref)]
 
@@ -374,6 +397,9 @@ def test_conv_gemm_x3_wide_tile(kind, monkeypatch):
                 out = torch.empty(1, cin, h, h, device=DEV)
                 modconv.gemm(g.to(DEV), out, phb, nphb, cout, cin, epi=modconv._epilogue(_hip.EPI_STORE))
             assert lib.smc_conv_gemm_last_x3() == (2 if form else 0)
+            assert _route() == ("conv_gemm_x3_kernel<1,4,8,1,16,2,0,true>" if form else
+                                "conv_gemm_lds_kernel<2,2,2,2,32,2>" if kind == "transposed" else
+                                "conv_gemm_lds_kernel<2,2,2,2,16,2>"), _route()
         return [(out, ref)]
 
     _both_forms(monkeypatch, run, f"wide tile {kind}")
@@ -604,8 +630,9 @@ def test_act_bwd_from_y(hw):
 
 def test_conv_gemm_2gib_input_fallback():
     """An input of >= 2 GiB (batch 16 of the r = 1024 conv1: 2.1 GB) exceeds the 32-bit buffer offsets of the
-    LDS-DMA / row-halo kernels and runs the register-staged kernel with 64-bit addressing: it must equal the
-    same conv computed in two halves of the batch (each < 2 GiB, the fast kernels), to fp32 summation order."""
+    LDS-DMA / row-halo kernels and runs the register-staged kernel with 64-bit addressing (asserted:
+    conv_gemm_kernel<1,4,1,1,16,false>): it must equal the same conv computed in two halves of the batch (each
+    < 2 GiB: not the register-staged kernel, asserted), to fp32 summation order."""
     from stylemc_amd import _hip, modconv
     gen = torch.Generator().manual_seed(12)
     n, cin, cout, r = 16, 32, 32, 1024
@@ -617,12 +644,14 @@ def test_conv_gemm_2gib_input_fallback():
     ph, nph, _, _ = P.fwd_phases(r, r)
     y = torch.empty(n, cout, r, r, device=DEV)
     modconv.gemm(x, y, ph, nph, cin, cout, s=s, epi=modconv._epilogue(_hip.EPI_STORE))
+    assert _route() == "conv_gemm_kernel<1,4,1,1,16,false>", _route()
     y2 = torch.empty_like(y)
     h = n // 2
     for sl in (slice(0, h), slice(h, n)):
         part = torch.empty(h, cout, r, r, device=DEV)
         modconv.gemm(x[sl].contiguous(), part, ph, nph, cin, cout, s=s[sl].contiguous(),
                      epi=modconv._epilogue(_hip.EPI_STORE))
+        assert not _route().startswith("conv_gemm_kernel<"), _route()
         y2[sl] = part
     err = ((y - y2).abs().max() / y2.abs().max()).item()
     assert err <= 2e-6, err
