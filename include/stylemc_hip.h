@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define SMC_ABI_VERSION 5
+#define SMC_ABI_VERSION 6
 
 #define SMC_OK 0
 #define SMC_ERR_INVALID 1     /* bad argument / shape (reference: TORCH_CHECK -> RuntimeError)   */
@@ -361,6 +361,39 @@ typedef struct {
 int64_t smc_linear_workspace_size(int M, int N, int K);
 int smc_linear_f32(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int M, int N, int K,
                    const smc_linear_epilogue* epi, float* workspace, int64_t workspace_bytes, void* stream);
+
+/* smc_linear_ex_f32: smc_linear_f32 with the three optional operands the tower's executor hands the same launch
+ * (tests, attribution), each NULL or:
+ *   bt       the same B transposed, [N][K] row-major with row pitch K, 16-B aligned: N % 64 == 0 && K % 64 == 0 shapes
+ *            stage the B tile k-fastest (lin_gemm2_kernel<true>);
+ *   planes   the split-bf16 planes of the same [K][N] (smc_linear_x3_planes, 16-B aligned): those shapes run the fp32
+ *            products as three-term bf16 splits (lin_gemm2_x3_kernel; planes take precedence over bt);
+ *   counters smc_linear_counter_ints(M, N) zeroed ints: a split-K call sums its partial tiles in the GEMM launch itself
+ *            (the workgroup that finishes a tile last; the counters are left non-zero), NULL: in a second kernel.
+ * Other shapes ignore bt and planes (the 32 x 128 exact-fp32 kernel). */
+int64_t smc_linear_counter_ints(int M, int N);
+int smc_linear_ex_f32(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int M, int N, int K,
+                      const smc_linear_epilogue* epi, float* workspace, int64_t workspace_bytes, const float* bt,
+                      const void* planes, int* counters, void* stream);
+/* Split-bf16 planes of a row-major [K][N] fp32 matrix (ldb floats per row; K % 32 == 0): b = t0 + t1 + t2 exactly,
+ * each term the top 16 bits of what the terms before it leave (truncation); term s of b[k][n] is the bf16 at element
+ * ((((k / 32) * 3 + s) * 4 + (k % 32) / 8) * N + n) * 8 + k % 8.  smc_linear_x3_planes_bytes: the buffer's size. */
+int64_t smc_linear_x3_planes_bytes(int K, int N);
+int smc_linear_x3_planes(const float* b, int ldb, int K, int N, void* planes, void* stream);
+
+/* Route report of this thread's last GEMM launch through smc_linear_f32, smc_linear_ex_f32 or the tower's executor
+ * (smc_vit_forward_f32 / smc_vit_backward_f32: their last projection); written at the launch site, no launch
+ * decision reads it.  Route: 0 ("none") when the call failed before its launch, otherwise the kernel, 1 ..
+ * smc_linear_route_count() - 1, named by smc_linear_route_name (NULL outside the range).  nsplit: the split-K factor
+ * of that launch (0 with route 0).  reduce: how its partial tiles were summed, */
+#define SMC_LIN_REDUCE_NONE 0     /* nsplit == 1: a single pass                 */
+#define SMC_LIN_REDUCE_KERNEL 1   /* the separate reduction kernel              */
+#define SMC_LIN_REDUCE_INLAUNCH 2 /* the in-launch hand-off (counters given)    */
+int smc_linear_last_route(void);
+int smc_linear_last_nsplit(void);
+int smc_linear_last_reduce(void);
+int smc_linear_route_count(void);
+const char* smc_linear_route_name(int route);
 
 /* LayerNorm over the last dim (nn.LayerNorm: biased variance, y = (x-mean)*rstd*w + b), one row per
  * wave; dim % 64 == 0, dim <= 1024.  mean/rstd [rows] may be NULL.  Row strides in floats. */

@@ -47,6 +47,7 @@ class VitConfig(ctypes.Structure):
 
 
 LIN_ACT_NONE, LIN_ACT_QUICKGELU = 0, 1
+LIN_REDUCE_NONE, LIN_REDUCE_KERNEL, LIN_REDUCE_INLAUNCH = 0, 1, 2
 
 P = c_void_p
 _SIGS = {
@@ -106,6 +107,15 @@ _SIGS = {
     "smc_clip_preprocess_nada_bwd_f32": (c_int, [P, P] + [c_int] * 6 + [P, P, P, P]),
     "smc_linear_workspace_size": (c_int64, [c_int, c_int, c_int]),
     "smc_linear_f32": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, P, c_int64, P]),
+    "smc_linear_counter_ints": (c_int64, [c_int, c_int]),
+    "smc_linear_ex_f32": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, P, c_int64, P, P, P, P]),
+    "smc_linear_x3_planes_bytes": (c_int64, [c_int, c_int]),
+    "smc_linear_x3_planes": (c_int, [P, c_int, c_int, c_int, P, P]),
+    "smc_linear_last_route": (c_int, []),
+    "smc_linear_last_nsplit": (c_int, []),
+    "smc_linear_last_reduce": (c_int, []),
+    "smc_linear_route_count": (c_int, []),
+    "smc_linear_route_name": (c_char_p, [c_int]),
     "smc_layernorm_fwd_f32": (c_int, [P, c_int64, P, P, P, c_int64, P, P, c_int, c_int, c_float, P]),
     "smc_layernorm_bwd_f32": (c_int, [P, c_int64, P, c_int64, P, P, P, P, c_int64, P, c_int64, c_int, c_int, P]),
     "smc_attention_fwd_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
@@ -149,7 +159,7 @@ def load(path=None):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        if lib.smc_abi_version() != 5:
+        if lib.smc_abi_version() != 6:
             raise RuntimeError("stylemc_amd: ABI version mismatch, rebuild the library")
         if path is None:
             _lib = lib

@@ -489,6 +489,12 @@ __global__ __launch_bounds__(256 * KW, 2) void lin_gemm2_kernel(LinParams p, int
 // consecutive k of one column) is one conflict-free ds_read_b128 per term; the A tile stays fp32 (its XOR-swizzled
 // image of lin_gemm2_kernel) and each wave splits its A fragment (8 consecutive k of one row) in registers, once for
 // the wave's two column blocks.
+// Two accumulators per column block: the leading product a0 b0 into `acc`, the five cross terms (<= 2^-7 of it) into
+// `lo`, added once after the K loop.  v_mfma_f32_16x16x32_bf16 rounds its fp32 accumulator four times (once per 8 k),
+// so all six products on one accumulator round the running result 24 times per 32 k against the exact-fp32 kernel's
+// 16 -- at K = 128 the (33, 64, 128) case of tests/linear_cases.py measured 3.26e-07 of the max against exact fp32's
+// 1.58e-07, past the project's 2x bound.  With the cross terms apart the running result is rounded 4 times per 32 k
+// and `lo`'s roundings are 2^-7 of its size (measured on that case: see DESIGN.md section 3, ViT GEMM routes).
 typedef short bf16x8v __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ void lin_split8(const float (&x)[8], bf16x8v (&t)[3]) {
@@ -590,6 +596,7 @@ __global__ __launch_bounds__(256, 2) void lin_gemm2_x3_kernel(LinParams p, const
 
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    f32x4 lo[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     const int i = lane & 15, g = lane >> 4;
     const int arow = wm * 16 + i;
     if (ks0 < ks1) issue(ks0, 0);
@@ -617,16 +624,18 @@ __global__ __launch_bounds__(256, 2) void lin_gemm2_x3_kernel(LinParams p, const
                         Bs + (((kc * 3 + s) * 4 + g) * L2N + wn * 32 + blk * 16 + i) * 8);
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk) {
-                acc[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[2], bt[blk][0], acc[blk], 0, 0, 0);
-                acc[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[1], bt[blk][1], acc[blk], 0, 0, 0);
-                acc[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[0], bt[blk][2], acc[blk], 0, 0, 0);
-                acc[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[1], bt[blk][0], acc[blk], 0, 0, 0);
-                acc[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[0], bt[blk][1], acc[blk], 0, 0, 0);
+                lo[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[2], bt[blk][0], lo[blk], 0, 0, 0);
+                lo[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[1], bt[blk][1], lo[blk], 0, 0, 0);
+                lo[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[0], bt[blk][2], lo[blk], 0, 0, 0);
+                lo[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[1], bt[blk][0], lo[blk], 0, 0, 0);
+                lo[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[0], bt[blk][1], lo[blk], 0, 0, 0);
                 acc[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[0], bt[blk][0], acc[blk], 0, 0, 0);
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk) acc[blk] += lo[blk];
     // epilogue and split-K hand-off: as lin_gemm2_kernel (the 16x16x32 C layout is the 16x16x4 one)
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
@@ -723,10 +732,30 @@ int64_t lin_ws_floats(int M, int N, int K) {
 #ifndef SMC_LIN_BT
 #define SMC_LIN_BT 1
 #endif
+
+// Route report (smc_linear_last_route / _last_nsplit / _last_reduce): the kernel lin_launch launched last on this
+// thread, its split-K factor and how the partial tiles were summed.  Written at the launch sites below, read by no
+// launch decision (tests, attribution).
+enum LinRoute { LR_NONE = 0, LR_GEMM, LR_GEMM2, LR_GEMM2_BT, LR_GEMM2_X3, LR_COUNT };
+const char* const kLinRouteNames[LR_COUNT] = {"none", "lin_gemm_kernel", "lin_gemm2_kernel<false>",
+                                              "lin_gemm2_kernel<true>", "lin_gemm2_x3_kernel"};
+thread_local int g_lin_route = LR_NONE;
+thread_local int g_lin_nsplit = 0;
+thread_local int g_lin_reduce = SMC_LIN_REDUCE_NONE;
+
+void lin_record(int route, const LinParams& p) {
+    g_lin_route = route;
+    g_lin_nsplit = p.nsplit;
+    g_lin_reduce = p.nsplit == 1 ? SMC_LIN_REDUCE_NONE : p.counters ? SMC_LIN_REDUCE_INLAUNCH : SMC_LIN_REDUCE_KERNEL;
+}
+
 // bt (optional): the same B transposed, [N][K] row-major with row pitch K; used by the v2 kernel (SMC_LIN_BT)
 int lin_launch(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int M, int N, int K,
                const smc_linear_epilogue* epi, float* ws, int64_t ws_bytes, hipStream_t st, int* counters = nullptr,
                const short* bx3 = nullptr, const float* bt = nullptr) {
+    g_lin_route = LR_NONE;
+    g_lin_nsplit = 0;
+    g_lin_reduce = SMC_LIN_REDUCE_NONE;
     int rc = lin_validate(a, lda, b, ldb, c, ldc, M, N, K);
     if (rc != SMC_OK) return rc;
     LinParams p{};
@@ -743,6 +772,7 @@ int lin_launch(const float* a, int lda, const float* b, int ldb, float* c, int l
     }
     if (v2 && bx3) {  // split-bf16 products (B given as planes over the same [K][N])
         const int mt = (int)smc::ceil_div(M, L2M), ntl = N / L2N;
+        lin_record(LR_GEMM2_X3, p);
         hipLaunchKernelGGL(lin_gemm2_x3_kernel, dim3((unsigned)(mt * ntl * p.nsplit)), dim3(256), 0, st, p, bx3, mt, ntl);
     } else if (v2) {
         const int mt = (int)smc::ceil_div(M, L2M), ntl = N / L2N;
@@ -750,14 +780,17 @@ int lin_launch(const float* a, int lda, const float* b, int ldb, float* c, int l
             LinParams q = p;
             q.b = bt;
             q.ldb = K;
+            lin_record(LR_GEMM2_BT, p);
             hipLaunchKernelGGL((lin_gemm2_kernel<SMC_LIN_NST, SMC_LIN_KW, true>), dim3((unsigned)(mt * ntl * p.nsplit)),
                                dim3(256 * SMC_LIN_KW), 0, st, q, mt, ntl);
         } else {
+            lin_record(LR_GEMM2, p);
             hipLaunchKernelGGL((lin_gemm2_kernel<SMC_LIN_NST, SMC_LIN_KW, false>), dim3((unsigned)(mt * ntl * p.nsplit)),
                                dim3(256 * SMC_LIN_KW), 0, st, p, mt, ntl);
         }
     } else {
         dim3 grid((unsigned)smc::ceil_div(M, LBM), (unsigned)smc::ceil_div(N, LBN), (unsigned)p.nsplit);
+        lin_record(LR_GEMM, p);
         hipLaunchKernelGGL(lin_gemm_kernel, grid, dim3(LNT), 0, st, p);
     }
     rc = smc::check_launch("smc_linear_f32");
@@ -1515,9 +1548,17 @@ int vit_validate(const smc_vit_config* cfg, int B) {
 
 smc_linear_epilogue epi_none() { return smc_linear_epilogue{}; }
 
-// Split-K partials are reduced by a separate epilogue kernel: measured on MI355X (B=4 ViT-B/32,
-// tools/bench_vit.py) the in-launch hand-off's per-workgroup L2 write-back of the freshly written slabs costs
-// more than the extra launch (fwd 3.06 vs 1.77 ms).
+// Split-K partials: the executor's GEMMs sum them in the launch itself (SMC_LIN_INLAUNCH = 1: write-through partial
+// stores, a ticket counter per tile, the last workgroup of a tile sums -- measured at lin_gemm2_kernel's hand-off);
+// smc_linear_f32 passes no counters, so its calls reduce with the separate lin_splitk_epilogue_kernel.  (The first
+// hand-off, a per-workgroup release fence whose L2 write-back cost more than the extra launch, fwd 3.06 vs 1.77 ms,
+// is the one lin_gemm_kernel still carries.)
+
+void lin_x3_planes_launch(const float* b, int ldb, int K, int N, short* out, hipStream_t st) {
+    const int64_t total = (int64_t)K * N;
+    hipLaunchKernelGGL(lin_x3_planes_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(total, 256), 8192)),
+                       dim3(256), 0, st, b, ldb, K, N, out);
+}
 }  // namespace
 
 // =================================================================================== C ABI: primitives
@@ -1530,6 +1571,51 @@ SMC_API int64_t smc_linear_workspace_size(int M, int N, int K) {
 SMC_API int smc_linear_f32(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int M, int N, int K,
                            const smc_linear_epilogue* epi, float* workspace, int64_t workspace_bytes, void* stream) {
     return lin_launch(a, lda, b, ldb, c, ldc, M, N, K, epi, workspace, workspace_bytes, smc::as_stream(stream));
+}
+
+SMC_API int64_t smc_linear_counter_ints(int M, int N) {
+    if (M < 1 || N < 1) return 0;
+    return lin_tiles(M, N);
+}
+
+SMC_API int smc_linear_ex_f32(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int M, int N, int K,
+                              const smc_linear_epilogue* epi, float* workspace, int64_t workspace_bytes,
+                              const float* bt, const void* planes, int* counters, void* stream) {
+    g_lin_route = LR_NONE;
+    g_lin_nsplit = 0;
+    g_lin_reduce = SMC_LIN_REDUCE_NONE;
+    SMC_CHECK((reinterpret_cast<uintptr_t>(bt) & 15) == 0 && (reinterpret_cast<uintptr_t>(planes) & 15) == 0,
+              "smc_linear_ex_f32: bt and planes must be 16-byte aligned");
+    return lin_launch(a, lda, b, ldb, c, ldc, M, N, K, epi, workspace, workspace_bytes, smc::as_stream(stream),
+                      counters, static_cast<const short*>(planes), bt);
+}
+
+SMC_API int64_t smc_linear_x3_planes_bytes(int K, int N) {
+    if (K < 1 || N < 1 || K % 32 != 0) return 0;
+    return (int64_t)K * N * 3 * (int64_t)sizeof(short);
+}
+
+SMC_API int smc_linear_x3_planes(const float* b, int ldb, int K, int N, void* planes, void* stream) {
+    SMC_CHECK(b && planes, "smc_linear_x3_planes: null pointer");
+    SMC_CHECK(K >= 1 && N >= 1 && ldb >= N, "smc_linear_x3_planes: bad shape K=%d N=%d ldb=%d", K, N, ldb);
+    if (K % 32 != 0) {
+        smc::set_error("smc_linear_x3_planes: needs K %% 32 == 0 (K=%d N=%d)", K, N);
+        return SMC_ERR_UNSUPPORTED;
+    }
+    lin_x3_planes_launch(b, ldb, K, N, static_cast<short*>(planes), smc::as_stream(stream));
+    return smc::check_launch("smc_linear_x3_planes");
+}
+
+SMC_API int smc_linear_last_route(void) { return g_lin_route; }
+
+SMC_API int smc_linear_last_nsplit(void) { return g_lin_nsplit; }
+
+SMC_API int smc_linear_last_reduce(void) { return g_lin_reduce; }
+
+SMC_API int smc_linear_route_count(void) { return LR_COUNT; }
+
+SMC_API const char* smc_linear_route_name(int route) {
+    return route >= 0 && route < LR_COUNT ? kLinRouteNames[route] : nullptr;
 }
 
 SMC_API int smc_layernorm_fwd_f32(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t ldy,
@@ -1607,9 +1693,7 @@ SMC_API int smc_vit_pack_x3(const smc_vit_config* cfg, float* packed, void* stre
     layout(d, packed, &w);
     hipStream_t st = smc::as_stream(stream);
     auto planes = [&](const float* b, int K, int N, const short* out) {
-        const int64_t total = (int64_t)K * N;
-        hipLaunchKernelGGL(lin_x3_planes_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(total, 256), 8192)),
-                           dim3(256), 0, st, b, N, K, N, const_cast<short*>(out));
+        lin_x3_planes_launch(b, N, K, N, const_cast<short*>(out), st);
     };
     const int D = d.D;
     planes(w.conv_wt, d.P, D, w.conv_wt3);
