@@ -241,6 +241,29 @@ int smc_modconv_blur_act_f32(const float* t, int nsplit, int64_t split_stride, f
                              int t_w, int t_pitch, int y_h, int y_w, const float* f, int fh, int fw, int padx0,
                              int pady0, float fgain, int flip, const smc_conv_epilogue* epi, void* stream);
 
+/* The whole up=2 modconv layer in one launch: the 4-phase stride-2 transposed 3x3 conv of smc_conv_gemm_f32 (same
+ * `phases`, split-bf16 planes wk_x3 required, s_in may be NULL), the 4x4 FIR (pad 1) and the MODACT epilogue of
+ * smc_modconv_blur_act_f32, with the raw conv output T = [n, cout, 2h+1, 2w+1] kept on chip.  x: [n, cin, h, w];
+ * y, epi->u_save: [n, cout, 2h, 2w]; epi->noise indexes y.  y (and u_save) are bit-identical to the unsplit
+ * smc_conv_gemm_f32 (STORE) + smc_modconv_blur_act_f32 pair.  Only the built-in [1,3,3,1] filter at gain 4 (f = NULL,
+ * fh = fw = 4, fgain = 4) and only the shapes smc_modconv_up2_supported() accepts (host logic: cin % 16 == 0,
+ * cout 32 or 64, input < 2 GiB); anything else returns SMC_ERR_UNSUPPORTED.  `workspace` holds the per-sample
+ * weights when s_in is set: the bytes smc_conv_gemm_workspace_size(n, cin, cout, 2h+1, 2w+1, phases, 4) reports
+ * suffice.  smc_modconv_up2_plan_ok(): whether the two-launch pair would run that shape as the fused kernel computes
+ * it -- without split-K at the planning batch (where it splits, the fused grid under-fills the chip too and the
+ * pair is the faster form) and with style-scaled weights (planes of at most 9 cout super-pixels may take a
+ * prescaled input instead, which rounds differently): the shapes at which the bit-identity above holds.
+ * Route report of the last call of this thread, as for smc_conv_gemm_f32: 0 ("none") when it failed before its
+ * launch, else the kernel instantiation (smc_modconv_up2_route_name; NULL outside the range). */
+int smc_modconv_up2_supported(int n, int cin, int cout, int h, int w);
+int smc_modconv_up2_plan_ok(int n, int cin, int cout, int h, int w);
+int smc_modconv_up2_f32(const float* x, int n, int cin, int h, int w, float* y, int cout,
+                        const smc_conv_phase* phases, int nphases, const float* s_in, const float* f, int fh, int fw,
+                        float fgain, const smc_conv_epilogue* epi, float* workspace, int64_t workspace_bytes,
+                        void* stream);
+int smc_modconv_up2_last_route(void);
+const char* smc_modconv_up2_route_name(int route);
+
 /* Backward of smc_modconv_blur_act_f32 in one pass: du = bias_act'(g; y re-derived from u) * d[n,o],
  * dt = adjoint FIR of du (pad (pady0, padx0) = (fh-1-p, fw-1-p) of the forward pad p, flip, gain fgain;
  * upfirdn2d.py:245-264 rule), and if dd != NULL: dd[n,o] += sum_hw dz*u.  g/u: [n,c,u_h,u_w],

@@ -86,6 +86,12 @@ _SIGS = {
     "smc_modconv_epilogue_f32": (c_int, [P, c_int, c_int64, P, c_int, c_int, c_int, c_int, P, P]),
     "smc_modconv_blur_act_f32": (c_int, [P, c_int, c_int64, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P,
                                          c_int, c_int, c_int, c_int, c_float, c_int, P, P]),
+    "smc_modconv_up2_supported": (c_int, [c_int] * 5),
+    "smc_modconv_up2_plan_ok": (c_int, [c_int] * 5),
+    "smc_modconv_up2_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, P, c_int, c_int, c_float, P,
+                                    P, c_int64, P]),
+    "smc_modconv_up2_last_route": (c_int, []),
+    "smc_modconv_up2_route_name": (c_char_p, [c_int]),
     "smc_modconv_blur_act_bwd_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int,
                                              c_int, c_int, c_int, c_float, c_int, P, P, c_int64, P]),
     "smc_modconv_blur_act_bwd_workspace_size": (c_int64, [c_int] * 6),

@@ -22,48 +22,15 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "convt_x3.hpp"
 
 namespace {
 
+// (PhaseDev, GemmParams, the split-bf16 fragments and the transposed conv's K loop: convt_x3.hpp, shared with the
+// fused up=2 kernel of convt_fir.hip)
+using namespace smc::cg;
+
 constexpr int BK = 16;   // K-step granularity the host requires (cin % 16 == 0)
-constexpr int NT = 256;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct PhaseDev {
-    int ntaps;
-    int dy[9];
-    int dx[9];
-    int in_stride;
-    int out_h, out_w, out_oy, out_ox, out_sy, out_sx;
-    const float* wk;
-    int64_t wstride;  // LDS-DMA kernel: floats between two samples' weights (0 = shared weights)
-    const short* wx3;    // split-bf16 kernel: the three-term bf16 planes of wk (x3_weights_kernel layout)
-    int64_t wx3_stride;  // bf16 elements between two samples' planes (0 = shared weights)
-};
-
-struct GemmParams {
-    const float* x;
-    int n, cin, in_h, in_w;
-    float* y;
-    int cout, y_h, y_w;
-    PhaseDev ph[4];
-    int nphases;
-    const float* s;
-    int mode;
-    const float* d;
-    const float* noise;
-    int64_t noise_nstride;
-    const float* noise_strength;
-    const float* bias;
-    int act;
-    float alpha, gain, clamp;
-    float* u_save;
-    smc::EpiExt ext;
-    int nsplit;
-    int64_t split_stride;
-    int per_sample;  // LDS-DMA kernel: blockIdx.x -> (sample, tile of that sample): no tile straddles two images
-    int ntn;         // LDS-DMA kernel: column tiles; grid.x = row tiles x ntn, XCD-swizzled (0: 2-D grid)
-};
 
 // Epilogue shared by the gather-GEMM kernels: lane owns column m, registers walk output channels.
 // The per-channel operands of the tile's BO channels (d[n, o] * scale_c[o] / scale_c[o], bias[o], alpha_c[o]) are
@@ -411,11 +378,6 @@ struct WeightDma {
     static constexpr int bytes = ww * 4;
 };
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <int WO, int WM, int TO, int TM, int BKT, int NST, int TAG = 0>
 __global__ __launch_bounds__(NT, 2) void conv_gemm_lds_kernel(GemmParams p) {
     static_assert(WO * WM == 4, "4 waves");
@@ -609,43 +571,8 @@ __global__ __launch_bounds__(NT, 2) void conv_gemm_lds_kernel(GemmParams p) {
 //     ds_read_b32, split in registers (4 VALU per value + 3 v_perm per pair) and reused by the wave's TO blocks.
 // The C/D layout of the 32x32x16 bf16 MFMA is that of the fp32 32x32x2 one, so gemm_epilogue is shared.
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-
-// a = t0 + t1 + t2 for each of 8 values, as three bf16x8 fragments (the high halves of a, a - t0, a - t0 - t1)
-__device__ __forceinline__ void x3_split8(const float (&x)[8], bf16x8 (&t)[3]) {
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const unsigned u = __float_as_uint(x[j]);
-        const float r1 = x[j] - __uint_as_float(u & 0xffff0000u);
-        const unsigned v = __float_as_uint(r1);
-        const float r2 = r1 - __uint_as_float(v & 0xffff0000u);
-        u0[j] = u;
-        u1[j] = v;
-        u2[j] = __float_as_uint(r2);
-    }
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 w0, w1, w2;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {  // (high half of element 2j) | (high half of element 2j + 1) << 16
-        w0[j] = __builtin_amdgcn_perm(u0[2 * j + 1], u0[2 * j], 0x07060302u);
-        w1[j] = __builtin_amdgcn_perm(u1[2 * j + 1], u1[2 * j], 0x07060302u);
-        w2[j] = __builtin_amdgcn_perm(u2[2 * j + 1], u2[2 * j], 0x07060302u);
-    }
-    t[0] = __builtin_bit_cast(bf16x8, w0);
-    t[1] = __builtin_bit_cast(bf16x8, w1);
-    t[2] = __builtin_bit_cast(bf16x8, w2);
-}
-
-// acc += a * b over the six split products, smallest first
-__device__ __forceinline__ f32x16 x3_mma(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
-}
+// (bf16x8, x3_split8 -- a = t0 + t1 + t2 as three bf16x8 fragments -- and x3_mma -- the six split products, smallest
+// first: convt_x3.hpp)
 
 // out[nn][t][ci / 16][s][(ci % 16) / 8][o][ci % 8] = term s of wk[t][ci][o] * (s_in ? s_in[nn][ci] : 1)
 __global__ __launch_bounds__(256) void x3_weights_kernel(const float* wk, const float* s_in, short* out, int ntaps,
@@ -1161,8 +1088,6 @@ template <> struct ShiftPhases<1> { static constexpr int n = 2; static constexpr
 template <> struct ShiftPhases<2> { static constexpr int n = 2; static constexpr int p[4] = {0, 2, 0, 0}; };
 template <> struct ShiftPhases<3> { static constexpr int n = 1; static constexpr int p[4] = {0, 0, 0, 0}; };
 
-__host__ __device__ constexpr int shift_nph(int s) { return s == 0 ? 4 : (s == 3 ? 1 : 2); }
-
 template <int S, int TO, int TM, int BKT, int BO, int BM>
 __device__ __forceinline__ void convt_mma(const float* Ws, const float* Xs, int wo, int wm, int kh, int l32,
                                           f32x16 (&acc)[4][TO][TM]) {
@@ -1359,15 +1284,7 @@ __global__ __launch_bounds__(NT, 1) void convt_gemm_kernel(GemmParams p, ConvTPa
 // barrier per step): the input slab by `buffer_load_dword ... lds` (lane = super-pixel, the buffer range check
 // zero-fills the out-of-image shifts), the phases' weight slabs by `global_load_lds_dwordx4`.  Style scaling
 // comes in the per-sample weights (wscale_kernel) or a prescaled input, as for the other LDS-DMA launches.
-struct ConvTTaps {
-    int tap[4][4];  // [shift][phase] -> tap index in phase `phase`'s packed weights (-1: phase unused)
-};
-
-template <int S>
-__host__ __device__ constexpr int shift_phase(int j) {
-    // j-th phase reading shift S (the ShiftPhases table as a constexpr function)
-    return S == 0 ? j : (S == 1 ? (j ? 1 : 0) : (S == 2 ? (j ? 2 : 0) : 0));
-}
+// (ConvTTaps, shift_nph, shift_phase: convt_x3.hpp)
 
 template <int S, int TO, int TM, int BKT, int BO, int BM>
 __device__ __forceinline__ void convt_lds_mma(const float* Ws, const float* Xs, int wo, int wm, int kh, int l32,
@@ -1557,19 +1474,9 @@ __global__ __launch_bounds__(NT, 2) void convt_lds_kernel(GemmParams p, ConvTTap
 // a wave splits each B fragment once and feeds it to every phase's A fragments.
 template <int WO, int WM, int TO, int TM>
 __global__ __launch_bounds__(NT, 2) void convt_x3_kernel(GemmParams p, ConvTTaps tt) {
-    static_assert(WO * WM == 4, "4 waves");
-    constexpr int BKT = 16;
-    constexpr int BO = WO * TO * 32;
-    constexpr int BM = WM * TM * 32;
-    constexpr int NCH = BM / 64;
-    static_assert(NCH >= 1 && NCH <= 4 && 4 % NCH == 0, "BM in {64,128,256}");
-    constexpr int RSTEP = 4 / NCH;
-    constexpr int XI = BKT * NCH / 4;
-    constexpr int PB = 6 * BO * 16;              // bytes of one phase's planes per step
-    static_assert(PB % 1024 == 0, "phase planes split into whole 1-KB DMAs");
-    constexpr int XB = BKT * BM * 4;
-    constexpr int STAGE = XB + 4 * PB;           // input slab + up to 4 phases' planes
-    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
+    typedef ConvTX3<WO, WM, TO, TM> C;
+    constexpr int BKT = C::BKT, BO = C::BO, BM = C::BM, NCH = C::NCH;
+    __shared__ __attribute__((aligned(16))) char smem[C::RING];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1601,7 +1508,7 @@ __global__ __launch_bounds__(NT, 2) void convt_x3_kernel(GemmParams p, ConvTTaps
     const int c_end = (int)((int64_t)cpk * (split + 1) / p.nsplit);
     const int ks_begin = 4 * c_begin, ks_end = 4 * c_end;
 
-    const int cw = wave % NCH, r0 = wave / NCH;
+    const int cw = wave % NCH;
     const int m = m0 + cw * 64 + lane;
     const bool mvalid = m < M;
     int nn = 0, a = 0, b = 0;
@@ -1611,95 +1518,11 @@ __global__ __launch_bounds__(NT, 2) void convt_x3_kernel(GemmParams p, ConvTTaps
         a = rem / gw;
         b = rem - a * gw;
     }
-    const int in_hw = p.in_h * p.in_w;
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.x, (short)0, (int)((int64_t)p.n * p.cin * in_hw * 4), 0x00020000);
-    const int xvbase = nn * p.cin * in_hw * 4;
     const int wn = m0 / hw_g;
-    const int c16n = p.cin / 16;
-
-    auto issue = [&](int ks, int slot) {
-        const int c = ks >> 2, sh = ks & 3;
-        const int ci0 = c * BKT;
-        const int iy = a - (sh & 1), ix = b - (sh >> 1);
-        const bool ok = mvalid && iy >= 0 && iy < p.in_h && ix >= 0 && ix < p.in_w;
-        const int voff = ok ? xvbase + (iy * p.in_w + ix) * 4 : 0x7ffffff0;
-        char* st = smem + slot * STAGE;
-        float* xs = reinterpret_cast<float*>(st);
-#pragma unroll
-        for (int j = 0; j < XI; ++j) {
-            const int row = r0 + RSTEP * j;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                xrsrc, (__attribute__((address_space(3))) void*)(xs + row * BM + cw * 64), 4, voff,
-                (ci0 + row) * in_hw * 4, 0, 0);
-        }
-        const int nph = shift_nph(sh);
-        for (int j = wave; j < nph * (PB / 1024); j += 4) {
-            const int pj = j / (PB / 1024);          // which phase of this shift
-            const int phase = sh == 0 ? pj : (sh == 1 ? (pj ? 1 : 0) : (sh == 2 ? (pj ? 2 : 0) : 0));
-            const int L = (j - pj * (PB / 1024)) * 64 + lane;
-            const int run = L / BO, o = L - run * BO;
-            const PhaseDev& q = p.ph[phase];
-            const short* src = q.wx3 + (q.wx3_stride ? (int64_t)wn * q.wx3_stride : 0) +
-                               ((((int64_t)tt.tap[sh][phase] * c16n + ci0 / 16) * 6 + run) * p.cout + o0 + o) * 8;
-            __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(st + XB + j * 1024),
-                                             16, 0, 0);
-        }
-    };
 
     f32x16 acc[4][TO][TM];
-#pragma unroll
-    for (int ph = 0; ph < 4; ++ph)
-#pragma unroll
-        for (int i = 0; i < TO; ++i)
-#pragma unroll
-            for (int j = 0; j < TM; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[ph][i][j][r] = 0.f;
-
+    convt_x3_loop<WO, WM, TO, TM>(p, tt, smem, mvalid, nn, a, b, wn, o0, ks_begin, ks_end, acc);
     const int kh = lane >> 5, l32 = lane & 31;
-    if (ks_begin < ks_end) issue(ks_begin, 0);
-    auto step = [&](auto S_, int ks) {
-        constexpr int S = decltype(S_)::value;
-        constexpr int NP = shift_nph(S);
-        wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const char* st = smem + (S & 1) * STAGE;
-        const float* xcol = reinterpret_cast<const float*>(st) + wm * TM * 32 + l32;
-        bf16x8 bt[TM][3];
-#pragma unroll
-        for (int j = 0; j < TM; ++j) {
-            float xv[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) xv[e] = xcol[(8 * kh + e) * BM + j * 32];
-            x3_split8(xv, bt[j]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (ks + 1 < ks_end) issue(ks + 1, (S + 1) & 1);
-#pragma unroll
-        for (int pj = 0; pj < NP; ++pj) {
-            const short* Wp = reinterpret_cast<const short*>(st + XB + pj * PB);
-            bf16x8 at[TO][3];
-#pragma unroll
-            for (int i = 0; i < TO; ++i)
-#pragma unroll
-                for (int s = 0; s < 3; ++s)
-                    at[i][s] = *reinterpret_cast<const bf16x8*>(Wp + (((s * 2 + kh) * BO) + wo * TO * 32 + i * 32 + l32) * 8);
-#pragma unroll
-            for (int i = 0; i < TO; ++i)
-#pragma unroll
-                for (int j = 0; j < TM; ++j)
-                    acc[shift_phase<S>(pj)][i][j] = x3_mma(at[i], bt[j], acc[shift_phase<S>(pj)][i][j]);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    };
-    for (int ks = ks_begin; ks < ks_end; ks += 4) {
-        step(std::integral_constant<int, 0>{}, ks);
-        step(std::integral_constant<int, 1>{}, ks + 1);
-        step(std::integral_constant<int, 2>{}, ks + 2);
-        step(std::integral_constant<int, 3>{}, ks + 3);
-    }
 
     float* dst = p.nsplit > 1 ? p.y + (int64_t)split * p.split_stride : p.y;
     const int64_t plane = (int64_t)p.y_h * p.y_w;
@@ -1799,20 +1622,31 @@ struct ConvTL {
     int bo, bm, id;
 };
 
+// The three shape predicates of that plan, each stated once: conv_gemm_impl and the fused up=2 launch's gate
+// (smc::convt_up2_shape_ok / convt_up2_plan_ok) both decide through them.
+// -- which shapes the kernel takes
+// measured (tools/bench_gemm.py, batch 4): r = 1024 (64 -> 32 ch) 615 -> 413 us, r = 512 (128 -> 64) 427 ->
+// 416 us against the per-phase kernel; from 128 output channels up the per-phase kernel stays ahead
+// (r = 256: 364 vs 434 us; the 4 phases' accumulators cost the wide tiles their occupancy)
+bool convt_lds_shape_ok(int n, int cin, int cout, int in_h, int in_w) {
+    return cin % 16 == 0 && cout % 32 == 0 && cout <= 64 && (int64_t)n * cin * in_h * in_w * 4 < (1LL << 31);
+}
+// -- its tile
+ConvTL convt_lds_tile(int cout) { return cout % 64 == 0 ? ConvTL{64, 128, 1} : ConvTL{32, 128, 0}; }
+// -- style-scaled (per-sample) weights: tiles restart at every image wherever one would straddle two
+bool convt_lds_per_sample(int in_h, int in_w, const ConvTL& c) { return ((int64_t)(in_h + 1) * (in_w + 1)) % c.bm != 0; }
+
 bool convt_lds_plan(int n, int cin, int cout, int in_h, int in_w, int y_h, int y_w, const smc_conv_phase* ph, int nph,
                     const smc_conv_epilogue* epi, ConvTTaps* tt, ConvTL* cfg) {
     ConvTParams q{};
     if (!convt_structure(cin, cout, in_h, in_w, y_h, y_w, ph, nph, epi, &q)) return false;
-    // measured (tools/bench_gemm.py, batch 4): r = 1024 (64 -> 32 ch) 615 -> 413 us, r = 512 (128 -> 64) 427 ->
-    // 416 us against the per-phase kernel; from 128 output channels up the per-phase kernel stays ahead
-    // (r = 256: 364 vs 434 us; the 4 phases' accumulators cost the wide tiles their occupancy)
-    if (cin % 16 != 0 || cout % 32 != 0 || cout > 64 || (int64_t)n * cin * in_h * in_w * 4 >= (1LL << 31)) return false;
+    if (!convt_lds_shape_ok(n, cin, cout, in_h, in_w)) return false;
     if (tt) {
         for (int sh = 0; sh < 4; ++sh)
             for (int k = 0; k < 4; ++k)
                 tt->tap[sh][k] = q.w[sh][k] ? (int)((q.w[sh][k] - ph[k].wk) / ((int64_t)cin * cout)) : -1;
     }
-    if (cfg) *cfg = cout % 64 == 0 ? ConvTL{64, 128, 1} : ConvTL{32, 128, 0};
+    if (cfg) *cfg = convt_lds_tile(cout);
     return true;
 }
 
@@ -1943,6 +1777,9 @@ bool small_tile_ok(int n, int cin, int cout, int in_h, int in_w, const smc_conv_
 // otherwise write n copies of a 512x512x9 weight tensor (37.7 MB at n = 4) or fall back to the
 // register-staged kernel.  Returns the floats to reserve (0: not a prescale shape); stride-1 phases
 // only, the phase output images bounding the input image (3x3 same conv, 4-phase transposed conv).
+// (the shape condition alone: the largest phase image no larger than the weights of one input channel)
+bool prescale_shape(int64_t hw, int taps_all, int cout) { return hw <= (int64_t)taps_all * cout; }
+
 int64_t prescale_floats(int n, int cin, int cout, const smc_conv_phase* ph, int nph) {
     int64_t hw = 0;
     int taps_all = 0;
@@ -1951,7 +1788,7 @@ int64_t prescale_floats(int n, int cin, int cout, const smc_conv_phase* ph, int 
         hw = std::max<int64_t>(hw, (int64_t)ph[i].out_h * ph[i].out_w);
         taps_all += ph[i].ntaps;
     }
-    return hw <= (int64_t)taps_all * cout ? (((int64_t)n * cin * hw + 63) / 64) * 64 : 0;
+    return prescale_shape(hw, taps_all, cout) ? (((int64_t)n * cin * hw + 63) / 64) * 64 : 0;
 }
 
 int validate(const float* x, int n, int cin, int in_h, int in_w, float* y, int cout, int y_h, int y_w,
@@ -2148,7 +1985,7 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
         cfg = 6;
         c = Cfg{256, 128};
     }
-    const bool t_per_sample = convt_lds && s_in && ((int64_t)(in_h + 1) * (in_w + 1)) % tl.bm != 0;
+    const bool t_per_sample = convt_lds && s_in && convt_lds_per_sample(in_h, in_w, tl);
     const int nsplit = convt_lds ? plan_split_convt_lds(n, cin, cout, in_h, in_w, tl, t_per_sample)
                                  : fused_t ? plan_split_convt(n, cin, cout, in_h, in_w)
                                            : plan_split(n, cin, cout, phases, nphases, c, tag ? kSplitPerCuAux : 2);
@@ -2444,6 +2281,64 @@ int conv_gemm_aux(const float* x, int n, int cin, int in_h, int in_w, float* y, 
                   float* workspace, int64_t workspace_bytes, void* stream) {
     return conv_gemm_impl(x, n, cin, in_h, in_w, y, cout, y_h, y_w, phases, nphases, s_in, epi, workspace,
                           workspace_bytes, stream, 1);
+}
+
+// ---- the fused up=2 launch (convt_fir.hip) runs convt_x3_kernel's conv: its shape conditions, plan and operands
+bool convt_up2_shape_ok(int n, int cin, int cout, int h, int w) {
+    // convt_lds_plan's condition on the shape (the phase structure is checked at the call)
+    return n >= 1 && h >= 1 && w >= 1 && cin >= 16 && cout >= 32 && convt_lds_shape_ok(n, cin, cout, h, w);
+}
+
+bool convt_up2_plan_ok(int n, int cin, int cout, int h, int w) {
+    // the dispatcher's own predicates (conv_gemm_impl), for a style-scaled call as modconv makes it
+    const ConvTL tl = convt_lds_tile(cout);
+    if (plan_split_convt_lds(n, cin, cout, h, w, tl, convt_lds_per_sample(h, w, tl)) != 1) return false;
+    // where it may scale x instead of the weights (its largest phase image, (h+1)(w+1), against the 9 taps), it rounds
+    // differently
+    return !prescale_shape((int64_t)(h + 1) * (w + 1), 9, cout);
+}
+
+int convt_up2_prepare(const float* x, int n, int cin, int h, int w, float* y, int cout, const smc_conv_phase* phases,
+                      int nphases, const float* s_in, float* workspace, int64_t workspace_bytes, void* stream,
+                      GemmParams* pp, ConvTTaps* tt) {
+    // (the phases describe the raw conv output T = [2h+1, 2w+1]; the launch's y is the [2h, 2w] layer output)
+    const int th = 2 * h + 1, tw = 2 * w + 1;
+    int rc = validate(x, n, cin, h, w, y, cout, th, tw, phases, nphases);
+    if (rc != SMC_OK) return rc;
+    ConvTL tl{};
+    if (!convt_up2_shape_ok(n, cin, cout, h, w) || !phases_x3(phases, nphases) ||
+        !convt_lds_plan(n, cin, cout, h, w, th, tw, phases, nphases, nullptr, tt, &tl)) {
+        set_error("smc_modconv_up2_f32: needs the 4-phase stride-2 transposed 3x3 conv with split-bf16 planes, "
+                  "cin %% 16 == 0, cout 32 or 64 and an input below 2 GiB");
+        return SMC_ERR_UNSUPPORTED;
+    }
+    GemmParams& p = *pp;
+    p.x = x; p.n = n; p.cin = cin; p.in_h = h; p.in_w = w;
+    p.cout = cout; p.y_h = th; p.y_w = tw;
+    p.nphases = nphases;
+    for (int i = 0; i < nphases; ++i) {
+        p.ph[i].ntaps = phases[i].ntaps;
+        p.ph[i].wk = phases[i].wk;
+        p.ph[i].wx3 = reinterpret_cast<const short*>(phases[i].wk_x3);
+        p.ph[i].wx3_stride = 0;
+    }
+    if (!s_in) return SMC_OK;
+    // the per-sample weights W * s as split-bf16 planes, [phase][n][planes of one sample] (as conv_gemm_impl)
+    const int64_t need = wsample_floats(n, cin, cout, phases, nphases) * (int64_t)sizeof(float);
+    SMC_CHECK(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
+              "smc_modconv_up2_f32: workspace %lld < %lld bytes (or not 16-B aligned)", (long long)workspace_bytes,
+              (long long)need);
+    short* wp = reinterpret_cast<short*>(workspace);
+    int64_t off = 0;
+    for (int i = 0; i < nphases; ++i) {
+        const int64_t per = (int64_t)phases[i].ntaps * cin * cout;
+        hipLaunchKernelGGL(x3_weights_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(per * n, 256), 4096)), dim3(256),
+                           0, as_stream(stream), phases[i].wk, s_in, wp + off, phases[i].ntaps, cin, cout, n);
+        p.ph[i].wx3 = wp + off;
+        p.ph[i].wx3_stride = per * 3;
+        off += per * 3 * n;
+    }
+    return check_launch("smc_modconv_up2_f32 (per-sample split weights)");
 }
 }  // namespace smc
 

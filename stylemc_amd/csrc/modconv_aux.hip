@@ -9,8 +9,12 @@
 // The forward replaces the bias_act / upfirdn2d / fma launches the reference issues after each
 // grouped conv ([upstream] SynthesisLayer.forward -> bias_act.py:153, upfirdn2d.py:237, fma.py:15).
 #include "common.hpp"
+#include "fir_epi.hpp"
 
 namespace {
+
+using smc::st_f2;
+using smc::std_taps;
 
 struct Epi {
     int mode;
@@ -244,18 +248,7 @@ __device__ __forceinline__ void load_taps(const float* f, int flip, float fgain,
             tp[jy][jx] = f[(flip ? jy : FH - 1 - jy) * FW + (flip ? jx : FW - 1 - jx)] * fgain;
 }
 
-// The synthesis' resample filter, setup_filter([1,3,3,1]) = k k^T / 64, times the conv0 FIR gain 4, as compile-time
-// constants k_i k_j / 16 (exact in fp32, equal bit for bit to the values load_taps reads and scales): the FMAs take
-// literal operands and the 16 taps need no registers (blur_act_v4: 140 -> fewer VGPRs, more waves per SIMD for a
-// memory-bound kernel).  Symmetric, so the flip does not matter.
-template <int FH, int FW>
-__device__ __forceinline__ void std_taps(float (&tp)[FH][FW]) {
-    constexpr float k[4] = {1.f, 3.f, 3.f, 1.f};
-#pragma unroll
-    for (int jy = 0; jy < FH; ++jy)
-#pragma unroll
-        for (int jx = 0; jx < FW; ++jx) tp[jy][jx] = k[jy] * k[jx] * 0.0625f;
-}
+// (std_taps, the built-in [1,3,3,1] taps at the conv0 gain as compile-time constants: fir_epi.hpp)
 
 // Forward conv0 epilogue: U = FIR(T) (1:1, pad (pady0, padx0)), y = epi(U); stores y and U.
 template <int FH, int FW>
@@ -375,16 +368,6 @@ __global__ __launch_bounds__(256) void blur_act_fast(const float* t, int nsplit,
 #ifndef SMC_BLUR_PIPE
 #define SMC_BLUR_PIPE 1
 #endif
-template <bool NT>
-__device__ __forceinline__ void st_f2(float* p, float2 v) {
-    if (NT) {
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        __builtin_nontemporal_store(f32x2{v.x, v.y}, reinterpret_cast<f32x2*>(p));   // one dwordx2 store
-    } else {
-        *reinterpret_cast<float2*>(p) = v;
-    }
-}
-
 // TPB: row tiles per workgroup (grid.y = ceil(row tiles / TPB)), NT: non-temporal y / u stores (nothing reads y / u
 // before the next layer's conv has streamed the whole plane set).  Measured (profiles/r04/blur_ab/, bit-identical y):
 // TPB 4 + NT 712 -> 650 us over the five conv0 layers; TPB 8 / 16 no better; the same on the backward lost (dT is read
@@ -481,7 +464,7 @@ __global__ __launch_bounds__(256, STDF ? SMC_BLUR_WGS : 1) void blur_act_v4(cons
         }
         // the synthesis' conv0 epilogue (lrelu with 0 <= alpha <= 1, gain, clamp >= 0) with the activation fixed at
         // compile time: max / min forms, bit-identical to smc::epi_y for finite values
-        const bool lrelu_clamp = e.act == SMC_ACT_LRELU && e.alpha >= 0.f && e.alpha <= 1.f && e.clamp >= 0.f;
+        const bool lrelu_clamp = smc::modact_lrelu_clamp(e.act, e.alpha, e.clamp);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int oy = oy0 + 4 * ty + i;
@@ -493,15 +476,7 @@ __global__ __launch_bounds__(256, STDF ? SMC_BLUR_WGS : 1) void blur_act_v4(cons
                 continue;
             }
             if (e.u_save) st_f2<NT>(e.u_save + plane + pix, u2);
-            float2 q;
-            if (lrelu_clamp) {
-                const float zx = __fmaf_rn(u2.x, dv, nz[i].x) + bv, zy = __fmaf_rn(u2.y, dv, nz[i].y) + bv;
-                q.x = smc::lrelu_gain_clamp(zx, e.alpha, e.gain, e.clamp);
-                q.y = smc::lrelu_gain_clamp(zy, e.alpha, e.gain, e.clamp);
-            } else {
-                q = make_float2(smc::epi_y(u2.x, dv, nz[i].x, bv, e.act, e.alpha, e.gain, e.clamp),
-                                smc::epi_y(u2.y, dv, nz[i].y, bv, e.act, e.alpha, e.gain, e.clamp));
-            }
+            const float2 q = smc::modact2(u2, dv, nz[i], bv, lrelu_clamp, e.act, e.alpha, e.gain, e.clamp);
             st_f2<NT>(y + plane + pix, q);
         }
     }

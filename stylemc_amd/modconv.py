@@ -251,6 +251,47 @@ def wino_flops(n, cin, cout, h, w):
     return 2.0 * n * cin * cout * (h // 2) * (w // 2) * 16
 
 
+# The up=2 layers whose transposed conv runs as the 4-phase split-bf16 kernel (32 / 64 output channels: the 512- and
+# 1024-px conv0) in one launch, smc_modconv_up2_f32: conv, 4x4 FIR and epilogue with the raw conv output T kept in
+# LDS instead of written to and re-read from HBM (bit-identical y / u).  Module switch, as WINOGRAD.
+FUSED_UP = True
+# Output widths that take it.  Measured per layer at batch 4 (tools/bench_up2.py, five repetitions each;
+# profiles/up2_fused/bench_up2.txt, the table in DESIGN.md section 3): 32 channels (r = 1024; 256-position tiles, 76 %
+# of the tile's T values used) 618.8-634.8 -> 507.7-516.4 us; 64 channels (r = 512; the accumulators allow
+# 128-position tiles only, 63.5 % used) 447.2-516.0 -> 447.3-490.0 us -- no gain, so that layer keeps the two launches
+# (the kernel and the C ABI serve both widths; tests cover both).
+FUSED_UP_COUT = (32,)
+
+
+def fused_up_ok(spec, n, cin, h, w):
+    """Whether the up=2 layer takes the fused launch: the built-in filter, split-bf16 planes (the exact-fp32 form has
+    no fused kernel and keeps the two launches), a supported shape, and a plan of the two-launch path that the fused
+    kernel reproduces bit for bit (smc_modconv_up2_plan_ok): where that path plans split-K the grid under-fills the
+    chip, and on planes smaller than the weights it may scale x instead of the weights -- those shapes stay on it."""
+    P = spec.packed
+    if not (FUSED_UP and spec.up == 2 and spec.std_filter and P.use_x3 and P.cout in FUSED_UP_COUT):
+        return False
+    lib = _hip.load()
+    if not (lib.smc_modconv_up2_supported(n, cin, P.cout, h, w) and lib.smc_modconv_up2_plan_ok(n, cin, P.cout, h, w)):
+        return False
+    return all(p is not None for p in P.x3_phases)
+
+
+def fused_up(x, y, phases, nph, cin, cout, s, epi, alg_flops=0.0, alg_bytes=0):
+    """One smc_modconv_up2_f32 launch.  alg_flops: the transposed conv's dense MACs x 2 (the halo recompute of the
+    tiles not counted); alg_bytes: x, y (and u), weights."""
+    n, _, h, w = x.shape
+    lib = _hip.load()
+    ws_bytes = lib.smc_conv_gemm_workspace_size(n, cin, cout, 2 * h + 1, 2 * w + 1, phases, nph)
+    ws = torch.empty(max(ws_bytes // 4, 1), device=x.device, dtype=torch.float32) if ws_bytes > 0 else None
+    tm = _hip.timer()
+    tok = tm.wrap(alg_flops, alg_bytes, kind="direct_x3") if tm is not None else None
+    _hip.call("smc_modconv_up2_f32", x.data_ptr(), n, cin, h, w, y.data_ptr(), cout, phases, nph, _hip.ptr(s), None,
+              4, 4, 4.0, ctypes.byref(epi), _hip.ptr(ws), ws_bytes, _hip.stream())
+    if tok is not None:
+        tm.finish(tok)
+
+
 def _epilogue(mode, d=None, noise=None, noise_nstride=0, strength=None, bias=None, act="linear", alpha=0.0,
               gain=1.0, clamp=-1.0, u_save=None):
     e = _hip.ConvEpilogue()
@@ -349,6 +390,10 @@ def _modconv_fwd(ctx, x, styles, spec, noise, strength, gain, clamp, need_dx, ne
         gemm(x, y, phases, nph, cin, P.cout, s=styles, epi=epi,
              alg_flops=conv_flops(n, cin, P.cout, r_h, r_w, P.k * P.k),
              alg_bytes=4 * x.numel() + 4 * y.numel() * (2 if u is not None else 1) + wbytes)
+    elif fused_up_ok(spec, n, cin, h, w):
+        fused_up(x, y, phases, nph, cin, P.cout, styles, epi,
+                 alg_flops=conv_flops(n, cin, P.cout, h, w, 9),
+                 alg_bytes=4 * x.numel() + 4 * y.numel() * (2 if u is not None else 1) + wbytes)
     else:
         t = torch.empty(n, P.cout, th, tw, device=x.device, dtype=torch.float32)
         gemm(x, t, phases, nph, cin, P.cout, s=styles, epi=_epilogue(_hip.EPI_STORE),
