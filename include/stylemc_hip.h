@@ -176,6 +176,28 @@ int smc_conv_gemm_aux_f32(const float* x, int n, int cin, int in_h, int in_w, fl
                           const smc_conv_phase* phases, int nphases, const float* s_in, const smc_conv_epilogue* epi,
                           float* workspace, int64_t workspace_bytes, void* stream);
 
+/* Convolution weight gradient (replaces the weight-gradient calls of torch_utils/ops/conv2d_gradfix.py, the cuDNN
+ * conv2d_weight / conv_transpose2d weight gradient behind its Conv2dGradWeight), an implicit GEMM on the exact-fp32
+ * MFMA with M = cout, N = cin x taps, K = n * out_h * out_w:
+ *   dw[o][i][ky][kx] = sum_{n,a,b} grad[n,o,a,b] * inp[n, i, a*stride + ky - pad_y, b*stride + kx - pad_x]
+ * (reads outside inp are 0): the weight gradient of the cross-correlation F.conv2d computes.  inp [n][cin][in_h][in_w],
+ * grad [n][cout][out_h][out_w], dw [cout][cin][kh][kw].  With the roles swapped -- inp = the gradient of a stride-2
+ * transposed conv's output [n][cout][2h+1][2w+1], grad = that layer's input x [n][cin][h][w], stride 2, pad 0 -- the
+ * result [cin][cout][kh][kw] is conv_transpose2d's weight gradient in its own layout.
+ * Supported: kh == kw in {1, 3}, stride in {1, 2}, pads in 0..2, any cin, cout >= 1 (tile edges are masked), any
+ * n, in_h, in_w >= 1 with out = (in + 2 pad - k) / stride + 1 and every tensor below 2 GiB; anything else returns
+ * SMC_ERR_INVALID from host-side validation, before any launch.  K is split across workgroups to fill the chip: each
+ * split writes a partial dw into `workspace` (smc_conv_wgrad_workspace_size() bytes, 0: no split) and a second kernel
+ * sums the partials in split order -- no atomics, bit-identical from run to run.  smc_conv_wgrad_last_nsplit(): the
+ * split count of this thread's last successful call (a record; no launch decision reads it).
+ * Added under ABI version 6 without a version bump: callers detect these three entry points by symbol. */
+int64_t smc_conv_wgrad_workspace_size(int n, int cin, int cout, int in_h, int in_w, int out_h, int out_w, int kh,
+                                      int kw, int stride);
+int smc_conv_wgrad_f32(const float* inp, int n, int cin, int in_h, int in_w, const float* grad, int cout, int out_h,
+                       int out_w, int kh, int kw, int stride, int pad_y, int pad_x, float* dw, float* workspace,
+                       int64_t workspace_bytes, void* stream);
+int smc_conv_wgrad_last_nsplit(void);
+
 /* Winograd F(2x2, 3x3) form of the 3x3 stride-1 pad-1 convolution (the SynthesisLayer conv1 forward and its
  * data gradient -- the one-phase smc_conv_gemm_f32 call with taps (dy, dx) in {-1,0,1}^2), same operands and
  * epilogue semantics (modes STORE / MODACT / PRELU / PRELU_GRAD / AFFINE, no split-K workspace):

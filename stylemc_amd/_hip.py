@@ -68,6 +68,10 @@ _SIGS = {
     "smc_conv_gemm_aux_workspace_size": (c_int64, [c_int, c_int, c_int, c_int, c_int, P, c_int]),
     "smc_conv_gemm_aux_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, c_int, P, P, P,
                                       c_int64, P]),
+    "smc_conv_wgrad_workspace_size": (c_int64, [c_int] * 10),
+    "smc_conv_wgrad_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                   c_int, P, P, c_int64, P]),
+    "smc_conv_wgrad_last_nsplit": (c_int, []),
     "smc_conv_weights_x3_bytes": (c_int64, [c_int, c_int, c_int]),
     "smc_conv_weights_x3": (c_int, [P, c_int, c_int, c_int, P, P]),
     "smc_conv3x3_wino_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
