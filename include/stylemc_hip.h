@@ -203,18 +203,43 @@ int smc_conv_wgrad_last_nsplit(void);
  * epilogue semantics (modes STORE / MODACT / PRELU / PRELU_GRAD / AFFINE, no split-K workspace):
  *   acc[n,o,y,x] = sum_{c,dy,dx} W[o][c][dy+1][dx+1] * s[n,c] * x[n, c, y+dy, x+dx]
  * uw holds the transformed taps written by smc_wino_weights_f32 (flip 0 for this forward form).
- * smc_conv3x3_wino_supported() says whether a shape has a kernel (cin % 8, cout % 32, w % 4 == 0, w >= 32,
- * h even, input < 2 GiB); unsupported shapes return SMC_ERR_UNSUPPORTED. */
+ * smc_conv3x3_wino_supported() says whether a shape has a kernel: n >= 1, cin % 8 == 0 (>= 8), cout % 32 == 0
+ * (>= 32), the input n cin h w below 2 GiB, and a block of 64 tiles (2 x 2 outputs each) that divides the image's
+ * tile grid -- 2 tile rows x 32 tile columns (w % 64 == 0 and h % 4 == 0) or, failing that, 4 x 16 (w % 32 == 0 and
+ * h % 8 == 0).  (h even, w % 4 == 0 and w >= 32 are implied but do not suffice: h = 6, w = 64 has no kernel.)
+ * Unsupported shapes return SMC_ERR_UNSUPPORTED. */
 int smc_conv3x3_wino_supported(int n, int cin, int cout, int h, int w);
 int smc_conv3x3_wino_f32(const float* x, int n, int cin, int h, int w, float* y, int cout, const float* uw,
                          const float* s_in, const smc_conv_epilogue* epi, void* stream);
 /* The same conv with split K for grids too small to fill the chip (smc_conv3x3_wino_workspace_size() > 0: fewer than
  * 512 work items): K splits write raw partial tiles into `workspace` and smc_modconv_epilogue_f32 sums them and
- * applies `epi`.  A NULL / too small workspace runs the single-pass kernel. */
+ * applies `epi`.  A NULL / too small workspace runs the single-pass kernel.
+ * smc_conv3x3_wino_workspace_size() = split bytes + fold bytes (0 for an unsupported shape):
+ *   split: with items = n * (h w / 256) * (cout / 32) work items (n: the planning batch, smc_set_plan_batch) and
+ *     cin / 8 K steps, the split count doubles from 1
+ *     while items * splits < 512 and the steps divide into 2 * splits parts of at least 8; splits > 1 take
+ *     splits * n * cout * h * w * 4 bytes rounded up to 256, else 0;
+ *   fold: n * cin * cout * 64 bytes of per-image taps with the style s[n, c] folded in when cin * cout <= 128 * 128
+ *     (used by a call that passes s_in and the workspace), else 0. */
 int64_t smc_conv3x3_wino_workspace_size(int n, int cin, int cout, int h, int w);
 int smc_conv3x3_wino_ws_f32(const float* x, int n, int cin, int h, int w, float* y, int cout, const float* uw,
                             const float* s_in, const smc_conv_epilogue* epi, float* workspace, int64_t workspace_bytes,
                             void* stream);
+/* Route report of the last smc_conv3x3_wino_f32 / smc_conv3x3_wino_ws_f32 call of this thread, as for
+ * smc_conv_gemm_f32 (tests, attribution; no launch decision reads it): the kernel instantiation, numbered 1 ..
+ * smc_conv3x3_wino_route_count() - 1 and named as written in its launch -- wino_kernel<TC,SM,EK> (TC tile columns of
+ * the block; SM 1: style scale in the kernel, 2: none; EK 0: generic epilogue, 1: MODACT lrelu + clamp, 2: MODACT
+ * linear, 3: split-K partials), wino_x3_kernel<EK> / wino_x3r_kernel<EK> -- by smc_conv3x3_wino_route_name (NULL
+ * outside the range); 0 ("none") when the call failed before its launch.  Flags: SMC_ROUTE_SPLIT_K, and
+ * SMC_ROUTE_WINO_FOLD when the style was folded into per-image taps in the workspace first (the launch then runs
+ * SM = 2).  smc_conv3x3_wino_last_nsplit(): the K splits of that launch (1: one pass).
+ * Added under ABI version 6 without a version bump: callers detect these entry points by symbol. */
+#define SMC_ROUTE_WINO_FOLD 16
+int smc_conv3x3_wino_last_route(void);
+int smc_conv3x3_wino_last_route_flags(void);
+int smc_conv3x3_wino_last_nsplit(void);
+int smc_conv3x3_wino_route_count(void);
+const char* smc_conv3x3_wino_route_name(int route);
 /* Experimental split-bf16 F(2x2) for cin = cout = 32, w % 64 == 0, h % 4 == 0 (the r = 1024 conv1), taken by
  * smc_conv3x3_wino_ws_f32 with its workspace when enabled: mode 0 off (the default: slower in the full step,
  * profiles/r06/wino_x3/README), 1 for the MODACT lrelu form, 2 also for the linear form.  Process-wide; returns the
@@ -228,11 +253,18 @@ int smc_wino_weights_f32(const float* w, int cout, int cin, int flip, float* uw,
 /* Winograd F(4x4, 3x3) form of the same convolution (4x4 output tiles, 36 multiplies per channel pair instead of
  * 144; interpolation points 0, +-1, +-2), same operands and epilogue semantics as smc_conv3x3_wino_f32 and the same
  * C-ABI contract (replaces the same grouped conv2d of conv2d_resample.py:147-154).  uw holds the taps written by
- * smc_wino4_weights_f32.  smc_conv3x3_wino4_supported(): cin % 4 == 0, w % 64 == 0, h % 8 == 0, cout % 64 == 0;
- * input and taps < 2 GiB.  x, y, uw, u_save and noise 16-B aligned (noise_nstride % 4 == 0). */
+ * smc_wino4_weights_f32.  smc_conv3x3_wino4_supported(): n >= 1, cin % 4 == 0 (>= 4), w % 64 == 0 (>= 64),
+ * h % 8 == 0 (>= 8), cout % 64 == 0 (>= 64); the input n cin h w and the taps 36 cin cout below 2 GiB.  x, y, uw, u_save and noise
+ * 16-B aligned (noise_nstride % 4 == 0). */
 int smc_conv3x3_wino4_supported(int n, int cin, int cout, int h, int w);
 int smc_conv3x3_wino4_f32(const float* x, int n, int cin, int h, int w, float* y, int cout, const float* uw,
                           const float* s_in, const smc_conv_epilogue* epi, void* stream);
+/* Route report of the last smc_conv3x3_wino4_f32 call of this thread, as smc_conv3x3_wino_last_route: one of the six
+ * wino4_kernel<SM,EK> (SM, EK as above; no split-K form), 0 ("none") when the call failed before its launch.  Added
+ * under ABI version 6 without a version bump: callers detect these entry points by symbol. */
+int smc_conv3x3_wino4_last_route(void);
+int smc_conv3x3_wino4_route_count(void);
+const char* smc_conv3x3_wino4_route_name(int route);
 /* w [cout][cin][3][3] -> uw [K][9][N][4] floats (36 * cin * cout, 16-B aligned), U = G g G^T (6x6) per (k, n) computed
  * in fp64 and rounded once, element (a, b) at xi = 6 b + a; flip as for smc_wino_weights_f32. */
 int smc_wino4_weights_f32(const float* w, int cout, int cin, int flip, float* uw, void* stream);

@@ -20,6 +20,7 @@ ACT_CODES = {"linear": 1, "relu": 2, "lrelu": 3, "tanh": 4, "sigmoid": 5, "elu":
              "swish": 9}
 EPI_STORE, EPI_MODACT, EPI_PRELU, EPI_PRELU_GRAD, EPI_AFFINE = 0, 1, 2, 3, 4
 ROUTE_SPLIT_K, ROUTE_PER_SAMPLE, ROUTE_PRESCALE, ROUTE_WSAMPLE = 1, 2, 4, 8
+ROUTE_WINO_FOLD = 16
 
 
 class ConvPhase(ctypes.Structure):
@@ -79,9 +80,17 @@ _SIGS = {
     "smc_conv3x3_wino_workspace_size": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "smc_set_wino_x3": (c_int, [c_int]),
     "smc_conv3x3_wino_ws_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P, c_int64, P]),
+    "smc_conv3x3_wino_last_route": (c_int, []),
+    "smc_conv3x3_wino_last_route_flags": (c_int, []),
+    "smc_conv3x3_wino_last_nsplit": (c_int, []),
+    "smc_conv3x3_wino_route_count": (c_int, []),
+    "smc_conv3x3_wino_route_name": (c_char_p, [c_int]),
     "smc_wino_weights_f32": (c_int, [P, c_int, c_int, c_int, P, P]),
     "smc_conv3x3_wino4_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "smc_conv3x3_wino4_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P]),
+    "smc_conv3x3_wino4_last_route": (c_int, []),
+    "smc_conv3x3_wino4_route_count": (c_int, []),
+    "smc_conv3x3_wino4_route_name": (c_char_p, [c_int]),
     "smc_wino4_weights_f32": (c_int, [P, c_int, c_int, c_int, P, P]),
     "smc_wino_sp_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "smc_wino_sp_workspace_size": (c_int64, [c_int, c_int, c_int, c_int, c_int]),

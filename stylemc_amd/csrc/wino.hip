@@ -539,7 +539,7 @@ __global__ __launch_bounds__(256) void wino_weights_kernel(const float* w, int c
 #define SMC_WINO_TC_MAX 32
 #endif
 int wino_tc(int h, int w) {
-    if (h % 2 || w % 4 || w < 32) return 0;
+    if (h < 2 || h % 2 || w % 4 || w < 32) return 0;
     for (int tc = SMC_WINO_TC_MAX; tc >= 16; tc /= 2)
         if ((w / 2) % tc == 0 && (h / 2) % (WBT / tc) == 0) return tc;
     return 0;
@@ -552,8 +552,36 @@ int wino_tc(int h, int w) {
 #ifndef SMC_WINO_PROBE
 #define SMC_WINO_PROBE 0
 #endif
+// Route report (smc_conv3x3_wino_last_route): one value per kernel instantiation smc_conv3x3_wino_ws_f32 can name,
+// the kernel template and its parameters as written in the launch being the identity.  A record only: no launch
+// decision reads it.
+#define SMC_WINO_ROUTES_SM(X, TC, SM) \
+    X("wino_kernel<" #TC "," #SM ",0>") X("wino_kernel<" #TC "," #SM ",1>") \
+    X("wino_kernel<" #TC "," #SM ",2>") X("wino_kernel<" #TC "," #SM ",3>")
+#define SMC_WINO_ROUTES_TC(X, TC) SMC_WINO_ROUTES_SM(X, TC, 1) SMC_WINO_ROUTES_SM(X, TC, 2)
+#define SMC_WINO_ROUTE_NAME(name) name,
+constexpr const char* kWinoRouteNames[] = {
+    "none",
+    SMC_WINO_ROUTES_TC(SMC_WINO_ROUTE_NAME, 64)
+    SMC_WINO_ROUTES_TC(SMC_WINO_ROUTE_NAME, 32)
+    SMC_WINO_ROUTES_TC(SMC_WINO_ROUTE_NAME, 16)
+    "wino_x3_kernel<1>", "wino_x3_kernel<2>", "wino_x3r_kernel<1>", "wino_x3r_kernel<2>",
+};
+#undef SMC_WINO_ROUTE_NAME
+constexpr int kWinoRouteCount = sizeof(kWinoRouteNames) / sizeof(kWinoRouteNames[0]);
+// wino_kernel<TC, SM, EK>: the 8 forms of TC = 64, then those of 32 and 16, SM-major
+constexpr int wino_route(int tc, int sm, int ek) { return 1 + ((tc == 64 ? 0 : tc == 32 ? 1 : 2) * 2 + (sm - 1)) * 4 + ek; }
+constexpr int kWinoRouteX3 = 25, kWinoRouteX3R = 27;   // + EK - 1
+static_assert(wino_route(16, 2, 3) == kWinoRouteX3 - 1 && kWinoRouteCount == kWinoRouteX3R + 2,
+              "the route list and the numbering agree");
+
+thread_local int g_wino_route = 0;
+thread_local int g_wino_flags = 0;   // SMC_ROUTE_SPLIT_K | SMC_ROUTE_WINO_FOLD of that launch
+thread_local int g_wino_nsplit = 0;  // its K splits (1: one pass)
+
 template <int TC, int SM, int EK>
 void launch_wino(const WinoParams& p, int64_t items, hipStream_t st) {
+    g_wino_route = wino_route(TC, SM, EK);
     hipLaunchKernelGGL((wino_kernel<TC, SM, EK, 0, SMC_WINO_PROBE>), dim3((unsigned)items, (unsigned)p.nsplit), dim3(256),
                        0, st, p);
 }
@@ -1271,10 +1299,13 @@ void launch_wino_x3(const WinoParams& p, const short* planes, int64_t nstride, h
         WinoParams q = p;
         q.gy = p.h / 2;
         const int per = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)q.gx * q.gy, smc::device_cu_count() / p.n));
+        g_wino_route = kWinoRouteX3R + EK - 1;
         hipLaunchKernelGGL(wino_x3r_kernel<EK>, dim3((unsigned)per, (unsigned)p.n), dim3(512), 0, st, q, planes, nstride);
-    } else
+    } else {
+        g_wino_route = kWinoRouteX3 + EK - 1;
         hipLaunchKernelGGL(wino_x3_kernel<EK>, dim3((unsigned)per_img, (unsigned)p.n), dim3(256), 0, st, p, planes,
                            nstride);
+    }
 }
 
 
@@ -1315,6 +1346,9 @@ SMC_API int smc_conv3x3_wino_f32(const float* x, int n, int cin, int h, int w, f
 SMC_API int smc_conv3x3_wino_ws_f32(const float* x, int n, int cin, int h, int w, float* y, int cout, const float* uw,
                                     const float* s_in, const smc_conv_epilogue* epi, float* workspace,
                                     int64_t workspace_bytes, void* stream) {
+    g_wino_route = 0;
+    g_wino_flags = 0;
+    g_wino_nsplit = 0;
     SMC_CHECK(x && y && uw, "smc_conv3x3_wino_f32: null pointer");
     if (!smc_conv3x3_wino_supported(n, cin, cout, h, w)) {
         smc::set_error("smc_conv3x3_wino_f32: no Winograd kernel for n=%d cin=%d cout=%d %dx%d", n, cin, cout, h, w);
@@ -1363,6 +1397,7 @@ SMC_API int smc_conv3x3_wino_ws_f32(const float* x, int n, int cin, int h, int w
         const int rc = smc::check_launch("smc_conv3x3_wino_ws_f32 (x3 planes)");
         if (rc != SMC_OK) return rc;
         const int64_t ns = s_in ? X3_UPLANE : 0;
+        g_wino_nsplit = 1;
         if (ek1) launch_wino_x3<1>(p, planes, ns, st);
         else launch_wino_x3<2>(p, planes, ns, st);
         return smc::check_launch("smc_conv3x3_wino_ws_f32 (x3)");
@@ -1381,11 +1416,15 @@ SMC_API int smc_conv3x3_wino_ws_f32(const float* x, int n, int cin, int h, int w
         p.u_nstride = (int64_t)cin * 16 * cout;
         p.s = nullptr;
         s_in = nullptr;
+        g_wino_flags |= SMC_ROUTE_WINO_FOLD;
     }
     p.nsplit = 1;
+    g_wino_nsplit = 1;
     if (split_bytes > 0 && ws_ok) {
         SMC_CHECK((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "smc_conv3x3_wino_ws_f32: workspace alignment");
         p.nsplit = wino_nsplit(n, cin, cout, h, w);
+        g_wino_nsplit = p.nsplit;
+        g_wino_flags |= SMC_ROUTE_SPLIT_K;
         p.split_stride = (int64_t)n * cout * h * w;
         p.ws = workspace;
         launch_wino_s<3>(s_in != nullptr, tc, p, items, st);
@@ -1401,4 +1440,16 @@ SMC_API int smc_conv3x3_wino_ws_f32(const float* x, int n, int cin, int h, int w
     else
         launch_wino_s<0>(s_in != nullptr, tc, p, items, st);
     return smc::check_launch("smc_conv3x3_wino_f32");
+}
+
+SMC_API int smc_conv3x3_wino_last_route(void) { return g_wino_route; }
+
+SMC_API int smc_conv3x3_wino_last_route_flags(void) { return g_wino_flags; }
+
+SMC_API int smc_conv3x3_wino_last_nsplit(void) { return g_wino_nsplit; }
+
+SMC_API int smc_conv3x3_wino_route_count(void) { return kWinoRouteCount; }
+
+SMC_API const char* smc_conv3x3_wino_route_name(int route) {
+    return route >= 0 && route < kWinoRouteCount ? kWinoRouteNames[route] : nullptr;
 }

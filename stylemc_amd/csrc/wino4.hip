@@ -428,8 +428,20 @@ __global__ __launch_bounds__(256) void wino4_weights_kernel(const float* w, int 
     }
 }
 
+// Route report (smc_conv3x3_wino4_last_route): one value per wino4_kernel<SM, EK> instantiation.  A record only: no
+// launch decision reads it.
+constexpr const char* kW4RouteNames[] = {
+    "none",
+    "wino4_kernel<1,0>", "wino4_kernel<1,1>", "wino4_kernel<1,2>",
+    "wino4_kernel<2,0>", "wino4_kernel<2,1>", "wino4_kernel<2,2>",
+};
+constexpr int kW4RouteCount = sizeof(kW4RouteNames) / sizeof(kW4RouteNames[0]);
+thread_local int g_w4_route = 0;
+
 template <int SM, int EK>
 void launch_w4(const Wino4Params& p, int64_t items, hipStream_t st) {
+    static_assert(1 + (SM - 1) * 3 + EK < kW4RouteCount, "the route list and the numbering agree");
+    g_w4_route = 1 + (SM - 1) * 3 + EK;
     hipLaunchKernelGGL((wino4_kernel<SM, EK>), dim3((unsigned)items), dim3(W4_THREADS), 0, st, p);
 }
 
@@ -440,7 +452,9 @@ void launch_w4_s(bool has_s, const Wino4Params& p, int64_t items, hipStream_t st
 }
 
 // work item = 64 output channels x 32 tiles (2 tile rows x 16 tile columns = 8 x 64 outputs)
-bool w4_shape_ok(int cout, int h, int w) { return w % 64 == 0 && w >= 64 && h % 8 == 0 && cout % 64 == 0; }
+bool w4_shape_ok(int cout, int h, int w) {
+    return w % 64 == 0 && w >= 64 && h % 8 == 0 && h >= 8 && cout % 64 == 0 && cout >= 64;
+}
 
 }  // namespace
 
@@ -462,6 +476,7 @@ SMC_API int smc_wino4_weights_f32(const float* w, int cout, int cin, int flip, f
 
 SMC_API int smc_conv3x3_wino4_f32(const float* x, int n, int cin, int h, int w, float* y, int cout, const float* uw,
                                   const float* s_in, const smc_conv_epilogue* epi, void* stream) {
+    g_w4_route = 0;
     SMC_CHECK(x && y && uw, "smc_conv3x3_wino4_f32: null pointer");
     if (!smc_conv3x3_wino4_supported(n, cin, cout, h, w)) {
         smc::set_error("smc_conv3x3_wino4_f32: no Winograd F(4x4) kernel for n=%d cin=%d cout=%d %dx%d", n, cin, cout,
@@ -501,4 +516,12 @@ SMC_API int smc_conv3x3_wino4_f32(const float* x, int n, int cin, int h, int w, 
     else
         launch_w4_s<0>(s_in != nullptr, p, items, st);
     return smc::check_launch("smc_conv3x3_wino4_f32");
+}
+
+SMC_API int smc_conv3x3_wino4_last_route(void) { return g_w4_route; }
+
+SMC_API int smc_conv3x3_wino4_route_count(void) { return kW4RouteCount; }
+
+SMC_API const char* smc_conv3x3_wino4_route_name(int route) {
+    return route >= 0 && route < kW4RouteCount ? kW4RouteNames[route] : nullptr;
 }

@@ -42,7 +42,10 @@ def _check(got, x64, w64, what):
     assert rel <= 1e-6, f"{what}: relative norm error {rel:.3e}"
 
 
-SHAPES = [  # n, cin, cout, h, w  (TC 16 / 32 / 64 block shapes, non-square, 512 channels, cin != cout)
+# n, cin, cout, h, w  (non-square, 512 channels, cin != cout).  Block shapes: TC 16 at w = 32 only, TC 32 at every
+# other width (wino_tc() with SMC_WINO_TC_MAX 32 never picks 64 tile columns; tests/test_gpu_wino_routes.py holds the
+# cases per block shape and asserts the kernel each one ran)
+SHAPES = [
     (2, 32, 32, 32, 32),
     (1, 64, 64, 64, 64),
     (2, 16, 32, 128, 128),
@@ -259,6 +262,13 @@ def x3_mode():
     lib.smc_set_wino_x3(prev)
 
 
+def _last_route():
+    """(kernel instantiation, flags, K splits) of this thread's last smc_conv3x3_wino_ws_f32 launch."""
+    lib = _lib().load()
+    return (lib.smc_conv3x3_wino_route_name(lib.smc_conv3x3_wino_last_route()).decode(),
+            lib.smc_conv3x3_wino_last_route_flags(), lib.smc_conv3x3_wino_last_nsplit())
+
+
 def _x3_ws(n, h, w):
     nb = _lib().load().smc_conv3x3_wino_workspace_size(n, 32, 32, h, w)
     assert nb == n * 16 * 3 * 2 * 4 * 16 * 8 * 2, "not the split-bf16 plan (96 KB of U planes per image)"
@@ -299,6 +309,7 @@ def test_wino_x3_vs_fp64(shape, x3_mode):
         y = torch.full((n, cout, h, w), float("nan"), device=DEV)
         H.call("smc_conv3x3_wino_ws_f32", xd.data_ptr(), n, cin, h, w, y.data_ptr(), cout, uw.data_ptr(),
                sd.data_ptr() if flip == 0 else None, ctypes.byref(plain), ws.data_ptr(), nb, H.stream())
+        assert _last_route() == ("wino_x3r_kernel<1>", 0, 1)   # the lrelu form (EK 1) of the register-U kernel
         torch.cuda.synchronize()
         assert torch.isfinite(y).all()
         if flip == 0:
@@ -336,6 +347,9 @@ def test_wino_x3_modact_vs_fp32_kernel(act, x3_mode):
         H.call("smc_conv3x3_wino_ws_f32", x.data_ptr(), n, c, h, w, y.data_ptr(), c,
                P.wino_weights(0 if act == "lrelu" else 1).data_ptr(), sp, ctypes.byref(epi),
                ws.data_ptr() if use_ws else None, nb if use_ws else 0, H.stream())
+        # with the planes: the split-bf16 kernel; without a workspace: the fp32 kernel, style scale in its transform
+        ek, sm = (1, 1) if act == "lrelu" else (2, 2)
+        assert _last_route() == ((f"wino_x3r_kernel<{ek}>" if use_ws else f"wino_kernel<32,{sm},{ek}>"), 0, 1)
         outs.append((y, u))
     torch.cuda.synchronize()
     (yx, ux), (yf, uf) = outs
