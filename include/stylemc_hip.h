@@ -152,8 +152,9 @@ int64_t smc_conv_gemm_workspace_size(int n, int cin, int cout, int y_h, int y_w,
 /* Route report of the last smc_conv_gemm_f32 / smc_conv_gemm_aux_f32 call of this thread (tests, attribution; no
  * launch decision reads it).  A route is one kernel instantiation of the dispatcher, numbered 1 ..
  * smc_conv_gemm_route_count() - 1 and named by its kernel template and parameters (smc_conv_gemm_route_name; NULL
- * outside the range); 0 ("none") when the call failed before its launch.  The flags are the modifiers of that
- * launch: */
+ * outside the range); 0 ("none") when the call failed before its launch.  The names are the stable identity of a
+ * route; the numbers are an index into the names for one build of the library and shift when a route is added or
+ * removed, so compare names, never numbers, across builds.  The flags are the modifiers of that launch: */
 #define SMC_ROUTE_SPLIT_K 1     /* split-K partial planes, summed by the epilogue pass                  */
 #define SMC_ROUTE_PER_SAMPLE 2  /* tiles restarted per image (style-scaled input, straddling tiles)      */
 #define SMC_ROUTE_PRESCALE 4    /* x * s written to the workspace, shared weights                        */
@@ -229,8 +230,9 @@ int smc_conv3x3_wino_ws_f32(const float* x, int n, int cin, int h, int w, float*
  * smc_conv_gemm_f32 (tests, attribution; no launch decision reads it): the kernel instantiation, numbered 1 ..
  * smc_conv3x3_wino_route_count() - 1 and named as written in its launch -- wino_kernel<TC,SM,EK> (TC tile columns of
  * the block; SM 1: style scale in the kernel, 2: none; EK 0: generic epilogue, 1: MODACT lrelu + clamp, 2: MODACT
- * linear, 3: split-K partials), wino_x3_kernel<EK> / wino_x3r_kernel<EK> -- by smc_conv3x3_wino_route_name (NULL
- * outside the range); 0 ("none") when the call failed before its launch.  Flags: SMC_ROUTE_SPLIT_K, and
+ * linear, 3: split-K partials), wino_x3r_kernel<EK> -- by smc_conv3x3_wino_route_name (NULL outside the range; the
+ * names are the stable identity, the numbers an index into them for one build); 0 ("none") when the call failed
+ * before its launch.  Flags: SMC_ROUTE_SPLIT_K, and
  * SMC_ROUTE_WINO_FOLD when the style was folded into per-image taps in the workspace first (the launch then runs
  * SM = 2).  smc_conv3x3_wino_last_nsplit(): the K splits of that launch (1: one pass).
  * Added under ABI version 6 without a version bump: callers detect these entry points by symbol. */

@@ -611,19 +611,6 @@ __global__ __launch_bounds__(256) void x3_weights_kernel(const float* wk, const 
 #ifndef SMC_X3_NST
 #define SMC_X3_NST 2
 #endif
-#ifndef SMC_X3_K32_SMALL
-#define SMC_X3_K32_SMALL 1
-#endif
-// Tiles whose waves each own all of the tile's output channels (WO = 1: 128 x 32 or 64 x 32 per wave instead of
-// 64 x 64 / 32 x 64): a B fragment is split once per workgroup instead of once per wave pair (A/B knob)
-#ifndef SMC_X3_WO1
-#define SMC_X3_WO1 1
-#endif
-// ... with 16-channel K steps (half the LDS per stage: 3 workgroups per CU instead of 2; A/B knob).  Measured
-// (profiles/r05/ab5/, two interleaved rounds on one box): 468.96 / 467.66 against 467.77 / 466.56 images/s.
-#ifndef SMC_X3_WO1_K16
-#define SMC_X3_WO1_K16 1
-#endif
 // Timing probes only (0 in the library; tools/ builds a variant with SMC_AB_DEFINES): 1 drops the input DMAs after
 // the first K step, 2 the weight DMAs after the first, 4 the register split (the fp32 bits reused as the three terms)
 #ifndef SMC_X3_PROBE
@@ -634,12 +621,9 @@ __global__ __launch_bounds__(256) void x3_weights_kernel(const float* wk, const 
 // are amortised over twice the MFMAs of the 128-channel tile (per wave and step: 8 input + 6 weight DMAs, 44 split
 // VALU for 48 MFMAs, against 8 + 3 and 44 for 24), the issue budget the 128-channel tile overruns.  The A fragments
 // are read one output block ahead of its MFMAs instead of all at once (128 accumulator registers leave no room for
-// 8 x 3 fragments).  Only where the 256-channel grid needs no split-K, for shared weights (A/B knob SMC_X3_WIDE).
+// 8 x 3 fragments).  Only where the 256-channel grid needs no split-K, for shared weights (plan_conv).
 // Measured it gains less than the issue count suggests (-5 % on the r = 256 data gradient, +2 % on the style-scaled
 // r = 128 forward): the 128-channel tile is not bound by its DMA + split issue alone.
-#ifndef SMC_X3_WIDE
-#define SMC_X3_WIDE 1
-#endif
 
 template <int WO, int WM, int TO, int TM, int BKT, int NST = SMC_X3_NST, int TAG = 0, bool AS = false>
 __global__ __launch_bounds__(NT, 2) void conv_gemm_x3_kernel(GemmParams p) {
@@ -1590,20 +1574,17 @@ bool convt_fusable(int cin, int cout, int in_h, int in_w, int y_h, int y_w, cons
     return cout <= 32 && convt_structure(cin, cout, in_h, in_w, y_h, y_w, ph, nph, epi, q);
 }
 
-struct ConvTCfg {
-    int bo, bm, id;
+// A workgroup tile: output channels x positions.
+struct Cfg {
+    int bo, bm;
 };
 
-ConvTCfg convt_cfg(int cout) {
-    if (cout % 128 == 0) return {128, 64, 0};
-    if (cout % 64 == 0) return {64, 128, 1};
-    // 32 x 128 tile: 159 VGPR + 80 AGPR -> 2 workgroups per CU (the 32 x 256 tile's 256 + 160 allow one):
-    // 763 -> 620 us on the r = 1024 conv0 (tools/bench_gemm.py)
-    return {32, 128, 3};
-}
+// Its one tile (convt_gemm_kernel<1,4,1,1,16>), 32 x 128: 159 VGPR + 80 AGPR -> 2 workgroups per CU (the 32 x 256
+// tile's 256 + 160 allow one): 763 -> 620 us on the r = 1024 conv0 (tools/bench_gemm.py)
+constexpr Cfg kConvTTile{32, 128};
 
 int plan_split_convt(int n, int cin, int cout, int in_h, int in_w) {
-    const ConvTCfg c = convt_cfg(cout);
+    const Cfg c = kConvTTile;
     const int64_t M = (int64_t)smc::plan_batch(n) * (in_h + 1) * (in_w + 1);
     const int64_t blocks = smc::ceil_div(M, c.bm) * smc::ceil_div(cout, c.bo);
     const int ks = 4 * (cin / BK);
@@ -1664,18 +1645,23 @@ int plan_split_convt_lds(int n, int cin, int cout, int in_h, int in_w, const Con
     return s < 1 ? 1 : s;
 }
 
-struct Cfg {
-    int bo, bm;
-};
+// The per-phase kernels' tiles.  pick_tile() chooses among the first three by cout; plan_conv() may then take the small
+// tile (small_tile_ok) or, for split-bf16 products, the wide one.
+enum Tile { TILE_NONE = -1, TILE_128x128, TILE_64x128, TILE_32x128, TILE_64x64, TILE_256x128 };
 
-int pick_cfg(int cout, Cfg* c) {
+constexpr Cfg tile_cfg(Tile t) {
+    constexpr Cfg dims[] = {{128, 128}, {64, 128}, {32, 128}, {64, 64}, {256, 128}};
+    return dims[t];
+}
+
+Tile pick_tile(int cout) {
     // 32/64-channel layers: 128-position tiles (twice the workgroups of the 256-position ones, half the LDS
     // per workgroup): r = 512 conv0 451 -> 424 us, r = 1024 bwd conv0 426 -> 396 us, the rest within 1 %
     // (tools/bench_gemm.py)
-    if (cout % 128 == 0) { *c = {128, 128}; return 0; }
-    if (cout % 64 == 0) { *c = {64, 128}; return 5; }
-    if (cout % 32 == 0 || cout == 16) { *c = {32, 128}; return 4; }  // cout 16: half-empty tile, masked
-    return -1;
+    if (cout % 128 == 0) return TILE_128x128;
+    if (cout % 64 == 0) return TILE_64x128;
+    if (cout % 32 == 0 || cout == 16) return TILE_32x128;  // cout 16: half-empty tile, masked
+    return TILE_NONE;
 }
 
 // Shared by the workspace query and the launch so both agree on the split.
@@ -1747,11 +1733,11 @@ int64_t wsample_floats(int n, int cin, int cout, const smc_conv_phase* ph, int n
 // (measured on MI355X, tools/bench_gemm.py, FFHQ-1024 shapes, batch 4): the occupancy hides the DMA latency
 // better than a deeper ring (total 12.6 vs 13.0 / 13.3 ms, register-staged kernel 13.2 ms).
 // BK = 32 for the wide tile on the long-K 512-channel layers.
-bool lds_bk32(int cfg, int cin) { return cfg == 0 && cin % 32 == 0 && cin >= 512; }
+bool lds_bk32(Tile tile, int cin) { return tile == TILE_128x128 && cin % 32 == 0 && cin >= 512; }
 
 // 64x64 tile (4 waves of one 32x32 block each) for GEMMs whose cout-based tile leaves most CUs idle (the
 // IR-SE50 7..28-px stages, the synthesis 4..32-px blocks): 4x the workgroups before any split-K, so fewer
-// and shorter partial planes.  LDS-DMA kernel only; SMC_NO_SMALL_TILE=1 disables (A/B knob).
+// and shorter partial planes.  LDS-DMA kernels only (the conditions below include lds_shape_ok for this tile).
 bool small_tile_ok(int n, int cin, int cout, int in_h, int in_w, const smc_conv_phase* ph, int nph, bool has_s,
                    const Cfg& base) {
     if (cout % 64 != 0) return false;
@@ -1766,7 +1752,7 @@ bool small_tile_ok(int n, int cin, int cout, int in_h, int in_w, const smc_conv_
     // 128x128 tile with split-K stays ahead from 128 tiles up (r = 32 conv1); below that the 64x64 tile wins on
     // the sum (synthesis GEMMs 12.14 ms at 128 vs 12.30 at 256; IR-SE50 pair 4.85 vs 5.06 ms at 32)
     if (blocks >= 128) return false;
-    const Cfg sm{64, 64};
+    const Cfg sm = tile_cfg(TILE_64x64);
     bool scaled_ok = false;
     if (!lds_shape_ok(n, cin, cout, in_h, in_w, ph, nph, sm, &scaled_ok)) return false;
     return !has_s || scaled_ok || (int64_t)taps_all * cout <= (int64_t)in_h * in_w;
@@ -1800,8 +1786,7 @@ int validate(const float* x, int n, int cin, int in_h, int in_w, float* y, int c
         smc::set_error("smc_conv_gemm_f32: cin=%d must be a multiple of %d", cin, BK);
         return SMC_ERR_UNSUPPORTED;
     }
-    Cfg c;
-    if (pick_cfg(cout, &c) < 0) {
+    if (pick_tile(cout) == TILE_NONE) {
         smc::set_error("smc_conv_gemm_f32: cout=%d must be 16 or a multiple of 32", cout);
         return SMC_ERR_UNSUPPORTED;
     }
@@ -1835,10 +1820,19 @@ namespace {
 #endif
 constexpr int kSplitPerCuAux = SMC_AUX_SPLIT_PER_CU;
 
+// Workspace layout: the split-K partial planes first, then (256-B aligned) the per-sample weights or the prescaled
+// input.  The one statement of where that second area starts, for the query and the launch.
+int64_t partials_offset(int nsplit, int64_t plane_elems) {
+    return nsplit > 1 ? ((nsplit * plane_elems * (int64_t)sizeof(float) + 255) / 256) * 256 : 0;
+}
+
+// The query knows neither the input size, nor whether the input is style-scaled, nor its alignment: it reserves for
+// a superset of plan_conv()'s launches, through the same tile and split functions.
 int64_t workspace_size_impl(int n, int cin, int cout, int y_h, int y_w, const smc_conv_phase* phases, int nphases,
                             int split_per_cu) {
-    Cfg c;
-    if (pick_cfg(cout, &c) < 0 || cin % BK != 0 || nphases < 1 || nphases > 4 || !phases) return 0;
+    const Tile tile = pick_tile(cout);
+    if (tile == TILE_NONE || cin % BK != 0 || nphases < 1 || nphases > 4 || !phases) return 0;
+    const Cfg c = tile_cfg(tile);
     int s;
     ConvTL tl;
     if (nphases == 4 && y_h % 2 == 1 && y_w % 2 == 1 &&
@@ -1850,15 +1844,16 @@ int64_t workspace_size_impl(int n, int cin, int cout, int y_h, int y_w, const sm
         s = plan_split_convt(n, cin, cout, (y_h - 1) / 2, (y_w - 1) / 2);
     else
         s = plan_split(n, cin, cout, phases, nphases, c, split_per_cu);
-    if (cout % 64 == 0) s = std::max(s, plan_split(n, cin, cout, phases, nphases, Cfg{64, 64}, split_per_cu));  // small tile
-    int64_t bytes = s > 1 ? (int64_t)s * n * cout * y_h * y_w * (int64_t)sizeof(float) : 0;
+    if (cout % 64 == 0) s = std::max(s, plan_split(n, cin, cout, phases, nphases, tile_cfg(TILE_64x64), split_per_cu));
+    const int64_t plane_elems = (int64_t)n * cout * y_h * y_w;
+    int64_t bytes = s > 1 ? s * plane_elems * (int64_t)sizeof(float) : 0;
     // the LDS-DMA kernel's per-sample weights when the input is style-scaled (the query does not know
     // whether it will be: reserve whenever the shape qualifies)
     bool scaled_ok = false;
     // (input size 1x1: the query reserves for a superset of the launches that use the area)
     const int64_t pre = prescale_floats(n, cin, cout, phases, nphases);
     if (lds_shape_ok(n, cin, cout, 1, 1, phases, nphases, c, &scaled_ok) || pre > 0)
-        bytes = ((bytes + 255) / 256) * 256 +
+        bytes = partials_offset(s, plane_elems) +
                 std::max(wsample_floats(n, cin, cout, phases, nphases), pre) * (int64_t)sizeof(float);
     return bytes;
 }
@@ -1875,148 +1870,290 @@ namespace {
 // whether the last conv_gemm_impl call of this thread launched split-bf16 products (smc_conv_gemm_last_x3)
 thread_local int g_last_x3 = 0;
 
-// Route report (smc_conv_gemm_last_route): one value per kernel instantiation conv_gemm_impl launches, the kernel
-// template and its parameters being the identity (NST: the SMC_X3_NST ring depth).  A record only: no launch
-// decision reads it.
-#define SMC_ROUTES(X)                                                   \
-    X(R_CONVT_X3_1421, "convt_x3_kernel<1,4,2,1>")                      \
-    X(R_CONVT_X3_2212, "convt_x3_kernel<2,2,1,2>")                      \
-    X(R_CONVT_X3_1411, "convt_x3_kernel<1,4,1,1>")                      \
-    X(R_CONVT_LDS_2212, "convt_lds_kernel<2,2,1,2,16>")                 \
-    X(R_CONVT_LDS_1411, "convt_lds_kernel<1,4,1,1,16>")                 \
-    X(R_CONVT_GEMM_2221, "convt_gemm_kernel<2,2,2,1,16>")               \
-    X(R_CONVT_GEMM_1421, "convt_gemm_kernel<1,4,2,1,16>")               \
-    X(R_CONVT_GEMM_1411, "convt_gemm_kernel<1,4,1,1,16>")               \
-    X(R_CONVT_GEMM_1412, "convt_gemm_kernel<1,4,1,2,16>")               \
-    X(R_X3_WIDE, "conv_gemm_x3_kernel<1,4,8,1,16,2,0,true>")            \
-    X(R_X3_1441_16, "conv_gemm_x3_kernel<1,4,4,1,16>")                  \
-    X(R_X3_1421_16, "conv_gemm_x3_kernel<1,4,2,1,16>")                  \
-    X(R_X3_1441_32, "conv_gemm_x3_kernel<1,4,4,1,32>")                  \
-    X(R_X3_1421_32, "conv_gemm_x3_kernel<1,4,2,1,32>")                  \
-    X(R_X3_2222_32_T1, "conv_gemm_x3_kernel<2,2,2,2,32,NST,1>")         \
-    X(R_X3_2222_32, "conv_gemm_x3_kernel<2,2,2,2,32>")                  \
-    X(R_X3_2222_16_T1, "conv_gemm_x3_kernel<2,2,2,2,16,NST,1>")         \
-    X(R_X3_2222_16, "conv_gemm_x3_kernel<2,2,2,2,16>")                  \
-    X(R_X3_2211_32_T1, "conv_gemm_x3_kernel<2,2,1,1,32,NST,1>")         \
-    X(R_X3_2211_16_T1, "conv_gemm_x3_kernel<2,2,1,1,16,NST,1>")         \
-    X(R_X3_2211_32, "conv_gemm_x3_kernel<2,2,1,1,32>")                  \
-    X(R_X3_2211_16, "conv_gemm_x3_kernel<2,2,1,1,16>")                  \
-    X(R_X3_1411_32, "conv_gemm_x3_kernel<1,4,1,1,32>")                  \
-    X(R_X3_1411_16, "conv_gemm_x3_kernel<1,4,1,1,16>")                  \
-    X(R_X3_2212_32, "conv_gemm_x3_kernel<2,2,1,2,32>")                  \
-    X(R_X3_2212_16, "conv_gemm_x3_kernel<2,2,1,2,16>")                  \
-    X(R_ROW_1412, "conv_row_kernel<1,4,1,2,8>")                         \
-    X(R_ROW_1422, "conv_row_kernel<1,4,2,2,8>")                         \
-    X(R_LDS_2222_32_T1, "conv_gemm_lds_kernel<2,2,2,2,32,2,1>")         \
-    X(R_LDS_2222_32, "conv_gemm_lds_kernel<2,2,2,2,32,2>")              \
-    X(R_LDS_2222_16_T1, "conv_gemm_lds_kernel<2,2,2,2,16,2,1>")         \
-    X(R_LDS_2222_16, "conv_gemm_lds_kernel<2,2,2,2,16,2>")              \
-    X(R_LDS_2211_32_T1, "conv_gemm_lds_kernel<2,2,1,1,32,2,1>")         \
-    X(R_LDS_2211_16_T1, "conv_gemm_lds_kernel<2,2,1,1,16,2,1>")         \
-    X(R_LDS_2211_16, "conv_gemm_lds_kernel<2,2,1,1,16,2>")              \
-    X(R_LDS_1411_16_T1, "conv_gemm_lds_kernel<1,4,1,1,16,2,1>")         \
-    X(R_LDS_1411_16, "conv_gemm_lds_kernel<1,4,1,1,16,2>")              \
-    X(R_LDS_2212_16_T1, "conv_gemm_lds_kernel<2,2,1,2,16,2,1>")         \
-    X(R_LDS_2212_16, "conv_gemm_lds_kernel<2,2,1,2,16,2>")              \
-    SMC_ROUTES_REG(X, 2222, "2,2,2,2")                                  \
-    SMC_ROUTES_REG(X, 1411, "1,4,1,1")                                  \
-    SMC_ROUTES_REG(X, 2212, "2,2,1,2")                                  \
-    SMC_ROUTES_REG(X, 2211, "2,2,1,1")
+// Route list: one row per kernel instantiation conv_gemm_impl can launch -- the enum id, the kernel template and its
+// arguments.  The name that smc_conv_gemm_route_name reports is those same tokens spelled out ("kernel<args>"), and the
+// launch goes through the function pointer that the row instantiates (kRoutes below), so the reported name and the
+// kernel that runs cannot differ.  The names are the stable identity of a route; the numbers
+// (smc_conv_gemm_last_route) are an index into the names for one build and shift whenever a row comes or goes.  A
+// route is added or removed by editing its row here and the one place in plan_conv() that selects it.  The report is
+// a record only: no launch decision reads it.  (Rows are written without blanks: the name is their spelling.)
+constexpr int NST = SMC_X3_NST;  // the split-bf16 ring depth, as the names spell it
+#define SMC_ROUTES(X)                                                \
+    X(R_CONVT_X3_1421, convt_x3_kernel, 1,4,2,1)                     \
+    X(R_CONVT_X3_1411, convt_x3_kernel, 1,4,1,1)                     \
+    X(R_CONVT_LDS_2212, convt_lds_kernel, 2,2,1,2,16)                \
+    X(R_CONVT_LDS_1411, convt_lds_kernel, 1,4,1,1,16)                \
+    X(R_CONVT_GEMM_1411, convt_gemm_kernel, 1,4,1,1,16)              \
+    X(R_X3_WIDE, conv_gemm_x3_kernel, 1,4,8,1,16,2,0,true)           \
+    X(R_X3_1441_16, conv_gemm_x3_kernel, 1,4,4,1,16)                 \
+    X(R_X3_1421_16, conv_gemm_x3_kernel, 1,4,2,1,16)                 \
+    X(R_X3_2222_32_T1, conv_gemm_x3_kernel, 2,2,2,2,32,NST,1)        \
+    X(R_X3_2222_16_T1, conv_gemm_x3_kernel, 2,2,2,2,16,NST,1)        \
+    X(R_X3_2211_32_T1, conv_gemm_x3_kernel, 2,2,1,1,32,NST,1)        \
+    X(R_X3_2211_16_T1, conv_gemm_x3_kernel, 2,2,1,1,16,NST,1)        \
+    X(R_X3_2211_32, conv_gemm_x3_kernel, 2,2,1,1,32)                 \
+    X(R_X3_2211_16, conv_gemm_x3_kernel, 2,2,1,1,16)                 \
+    X(R_X3_1411_32, conv_gemm_x3_kernel, 1,4,1,1,32)                 \
+    X(R_X3_1411_16, conv_gemm_x3_kernel, 1,4,1,1,16)                 \
+    X(R_X3_2212_32, conv_gemm_x3_kernel, 2,2,1,2,32)                 \
+    X(R_X3_2212_16, conv_gemm_x3_kernel, 2,2,1,2,16)                 \
+    X(R_ROW_1412, conv_row_kernel, 1,4,1,2,8)                        \
+    X(R_ROW_1422, conv_row_kernel, 1,4,2,2,8)                        \
+    X(R_LDS_2222_32_T1, conv_gemm_lds_kernel, 2,2,2,2,32,2,1)        \
+    X(R_LDS_2222_32, conv_gemm_lds_kernel, 2,2,2,2,32,2)             \
+    X(R_LDS_2222_16_T1, conv_gemm_lds_kernel, 2,2,2,2,16,2,1)        \
+    X(R_LDS_2222_16, conv_gemm_lds_kernel, 2,2,2,2,16,2)             \
+    X(R_LDS_2211_32_T1, conv_gemm_lds_kernel, 2,2,1,1,32,2,1)        \
+    X(R_LDS_2211_16_T1, conv_gemm_lds_kernel, 2,2,1,1,16,2,1)        \
+    X(R_LDS_2211_16, conv_gemm_lds_kernel, 2,2,1,1,16,2)             \
+    X(R_LDS_1411_16_T1, conv_gemm_lds_kernel, 1,4,1,1,16,2,1)        \
+    X(R_LDS_1411_16, conv_gemm_lds_kernel, 1,4,1,1,16,2)             \
+    X(R_LDS_2212_16_T1, conv_gemm_lds_kernel, 2,2,1,2,16,2,1)        \
+    X(R_LDS_2212_16, conv_gemm_lds_kernel, 2,2,1,2,16,2)             \
+    SMC_ROUTES_REG(X, 2222, 2,2,2,2)                                 \
+    SMC_ROUTES_REG(X, 1411, 1,4,1,1)                                 \
+    SMC_ROUTES_REG(X, 2212, 2,2,1,2)
 // the register-staged kernel's six forms per tile: BK 32 / 16, buffer loads (input < 2 GiB) or 64-bit addressing, TAG
-#define SMC_ROUTES_REG(X, T, S)                                         \
-    X(R_REG_##T##_32_BUF_T1, "conv_gemm_kernel<" S ",32,true,1>")       \
-    X(R_REG_##T##_16_BUF_T1, "conv_gemm_kernel<" S ",16,true,1>")       \
-    X(R_REG_##T##_32_BUF, "conv_gemm_kernel<" S ",32,true>")            \
-    X(R_REG_##T##_32, "conv_gemm_kernel<" S ",32,false>")               \
-    X(R_REG_##T##_16_BUF, "conv_gemm_kernel<" S ",16,true>")            \
-    X(R_REG_##T##_16, "conv_gemm_kernel<" S ",16,false>")
+#define SMC_ROUTES_REG(X, T, WO, WM, TO, TM)                         \
+    X(R_REG_##T##_32_BUF_T1, conv_gemm_kernel, WO,WM,TO,TM,32,true,1) \
+    X(R_REG_##T##_16_BUF_T1, conv_gemm_kernel, WO,WM,TO,TM,16,true,1) \
+    X(R_REG_##T##_32_BUF, conv_gemm_kernel, WO,WM,TO,TM,32,true)     \
+    X(R_REG_##T##_32, conv_gemm_kernel, WO,WM,TO,TM,32,false)        \
+    X(R_REG_##T##_16_BUF, conv_gemm_kernel, WO,WM,TO,TM,16,true)     \
+    X(R_REG_##T##_16, conv_gemm_kernel, WO,WM,TO,TM,16,false)
 
 enum Route {
     R_NONE = 0,
-#define SMC_ROUTE_ENUM(id, name) id,
+#define SMC_ROUTE_ENUM(id, ...) id,
     SMC_ROUTES(SMC_ROUTE_ENUM)
 #undef SMC_ROUTE_ENUM
     kRouteCount
 };
 
-constexpr const char* kRouteNames[] = {
-    "none",
-#define SMC_ROUTE_NAME(id, name) name,
-    SMC_ROUTES(SMC_ROUTE_NAME)
-#undef SMC_ROUTE_NAME
-};
-static_assert(sizeof(kRouteNames) / sizeof(kRouteNames[0]) == kRouteCount, "one name per route");
-static_assert(R_REG_2211_16 == kRouteCount - 1, "the route list and the enum agree");
-
 thread_local int g_last_route = R_NONE;
 thread_local int g_last_flags = 0;  // SMC_ROUTE_* modifiers of that launch (smc_conv_gemm_last_route_flags)
 
-int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y, int cout, int y_h, int y_w,
-                   const smc_conv_phase* phases, int nphases, const float* s_in, const smc_conv_epilogue* epi,
-                   float* workspace, int64_t workspace_bytes, void* stream, int tag) {
-    g_last_x3 = 0;
-    g_last_route = R_NONE;
-    g_last_flags = 0;
-    int rc = validate(x, n, cin, in_h, in_w, y, cout, y_h, y_w, phases, nphases);
-    if (rc != SMC_OK) return rc;
-    Cfg c;
-    int cfg = pick_cfg(cout, &c);
-    ConvTParams ctp{};
-    ConvTTaps ctt{};
-    ConvTL tl{};
+// ---- plan: everything the dispatcher decides, from the call's arguments alone (no launch, no write)
+enum Family { F_CONVT_LDS, F_CONVT_REG, F_X3, F_ROW, F_LDS, F_REG };
+constexpr const char* kFamilyWhat[] = {"smc_conv_gemm_f32 (fused transposed conv, LDS-DMA)",
+                                       "smc_conv_gemm_f32 (fused transposed conv)",
+                                       "smc_conv_gemm_f32 (split-bf16)",
+                                       "smc_conv_gemm_f32 (row-halo)",
+                                       "smc_conv_gemm_f32 (LDS-DMA)",
+                                       "smc_conv_gemm_f32"};
+
+struct Plan {
+    Family family;
+    Tile tile;        // the per-phase families' tile (the transposed-conv families: tl / kConvTTile)
+    ConvTL tl;        // F_CONVT_LDS
+    int bk;           // channels per K step
+    bool tag1, buf;   // the kernel's TAG 1 form; F_REG: raw buffer loads
+    int nsplit;
+    int flags;        // SMC_ROUTE_*
+    bool prescale;    // x * s goes to the workspace first and the GEMM runs with the shared weights
+    bool wsample;     // per-sample weights W * s are built in the workspace (else a style-scaling kernel scales in-loop)
+    bool per_sample;  // tiles restart at every image
+    int64_t pre_fl;   // floats of the prescaled input
+    int64_t max_m;    // positions of the largest phase
+    dim3 grid;
+    int ntn;          // column tiles, for the kernels that decode a one-dimensional grid
+    int x3;           // smc_conv_gemm_last_x3: 0, 1 split-bf16 products, 2 their wide tile
+    Route route;      // R_NONE: no kernel takes this plan
+    RowTaps rt;       // F_ROW
+    ConvTTaps ctt;    // F_CONVT_LDS
+    ConvTParams ctp;  // F_CONVT_REG
+};
+
+Plan plan_conv(const float* x, int n, int cin, int in_h, int in_w, int cout, int y_h, int y_w,
+               const smc_conv_phase* phases, int nphases, bool has_s, const smc_conv_epilogue* epi, int tag) {
+    Plan pl{};
+    Tile tile = pick_tile(cout);
+    Cfg c = tile_cfg(tile);
     const bool x3 = phases_x3(phases, nphases);  // split-bf16 products (the caller passed wk_x3 planes)
-    const bool convt_lds = convt_lds_plan(n, cin, cout, in_h, in_w, y_h, y_w, phases, nphases, epi, &ctt, &tl);
-    const bool fused_t = !convt_lds && convt_fusable(cin, cout, in_h, in_w, y_h, y_w, phases, nphases, epi, &ctp);
-    const int64_t pre_fl = prescale_floats(n, cin, cout, phases, nphases);
-    const bool prescale = s_in && !fused_t && pre_fl > 0 && (int64_t)n * cin * in_h * in_w <= pre_fl &&
-                          (in_h * in_w) % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    const float* s_prescale = s_in;
-    if (prescale) s_in = nullptr;  // the GEMM reads x * s from the workspace with the shared weights
-    if (!fused_t && !convt_lds && small_tile_ok(n, cin, cout, in_h, in_w, phases, nphases, s_in != nullptr, c)) {
-        cfg = 3;
-        c = Cfg{64, 64};
+    const bool convt_lds = convt_lds_plan(n, cin, cout, in_h, in_w, y_h, y_w, phases, nphases, epi, &pl.ctt, &pl.tl);
+    const bool fused_t = !convt_lds && convt_fusable(cin, cout, in_h, in_w, y_h, y_w, phases, nphases, epi, &pl.ctp);
+    pl.pre_fl = prescale_floats(n, cin, cout, phases, nphases);
+    pl.prescale = has_s && !fused_t && pl.pre_fl > 0 && (int64_t)n * cin * in_h * in_w <= pl.pre_fl &&
+                  (in_h * in_w) % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    if (pl.prescale) has_s = false;  // the GEMM reads x * s from the workspace with the shared weights
+    if (!fused_t && !convt_lds && small_tile_ok(n, cin, cout, in_h, in_w, phases, nphases, has_s, c)) {
+        tile = TILE_64x64;
+        c = tile_cfg(tile);
     }
     // split-bf16 wide tiles (conv_gemm_x3_kernel AS): 256 output channels where that grid fills the chip unsplit, for
     // shared weights only.  Measured (profiles/r05/x3_wide/, tools/bench_gemm.py): the r = 256 stride-2 data gradient
     // 226.3 -> 215.6 us; the style-scaled r = 128 transposed conv0 (per-sample weights) 259.9 -> 265.2, so not there.
-    if (SMC_X3_WIDE && x3 && !tag && !s_in && cfg == 0 && !fused_t && !convt_lds && cout % 256 == 0 &&
-        plan_split(n, cin, cout, phases, nphases, Cfg{256, 128}) == 1 &&
-        lds_shape_ok(n, cin, cout, in_h, in_w, phases, nphases, Cfg{256, 128}, nullptr)) {
-        cfg = 6;
-        c = Cfg{256, 128};
+    if (x3 && !tag && !has_s && tile == TILE_128x128 && !fused_t && !convt_lds && cout % 256 == 0 &&
+        plan_split(n, cin, cout, phases, nphases, tile_cfg(TILE_256x128)) == 1 &&
+        lds_shape_ok(n, cin, cout, in_h, in_w, phases, nphases, tile_cfg(TILE_256x128), nullptr)) {
+        tile = TILE_256x128;
+        c = tile_cfg(tile);
     }
-    const bool t_per_sample = convt_lds && s_in && convt_lds_per_sample(in_h, in_w, tl);
-    const int nsplit = convt_lds ? plan_split_convt_lds(n, cin, cout, in_h, in_w, tl, t_per_sample)
-                                 : fused_t ? plan_split_convt(n, cin, cout, in_h, in_w)
-                                           : plan_split(n, cin, cout, phases, nphases, c, tag ? kSplitPerCuAux : 2);
-    const int64_t plane_elems = (int64_t)n * cout * y_h * y_w;
-    if (nsplit > 1) {
-        const int64_t need = nsplit * plane_elems * (int64_t)sizeof(float);
-        SMC_CHECK(workspace && workspace_bytes >= need, "smc_conv_gemm_f32: workspace %lld < %lld bytes",
-                  (long long)workspace_bytes, (long long)need);
+    pl.tile = tile;
+    pl.bk = 16;
+    const bool t_per_sample = convt_lds && has_s && convt_lds_per_sample(in_h, in_w, pl.tl);
+    pl.nsplit = convt_lds ? plan_split_convt_lds(n, cin, cout, in_h, in_w, pl.tl, t_per_sample)
+                          : fused_t ? plan_split_convt(n, cin, cout, in_h, in_w)
+                                    : plan_split(n, cin, cout, phases, nphases, c, tag ? kSplitPerCuAux : 2);
+    if (pl.nsplit > 1) pl.flags |= SMC_ROUTE_SPLIT_K;
+    if (pl.prescale) pl.flags |= SMC_ROUTE_PRESCALE;
+    for (int i = 0; i < nphases; ++i)
+        pl.max_m = std::max(pl.max_m, (int64_t)n * phases[i].out_h * phases[i].out_w);
+
+    if (convt_lds) {
+        pl.family = F_CONVT_LDS;
+        pl.wsample = has_s;
+        pl.per_sample = t_per_sample;
+        const int64_t hw_g = (int64_t)(in_h + 1) * (in_w + 1);
+        const int64_t mt = t_per_sample ? n * smc::ceil_div(hw_g, pl.tl.bm) : smc::ceil_div(n * hw_g, pl.tl.bm);
+        pl.ntn = cout / pl.tl.bo;
+        pl.grid = dim3((unsigned)(mt * pl.ntn), 1, (unsigned)pl.nsplit);
+        pl.x3 = x3 ? 1 : 0;
+        // split-bf16: waves that each own all of the tile's output channels (WO = 1, as for the per-phase tiles below)
+        pl.route = x3 ? (pl.tl.id == 1 ? R_CONVT_X3_1421 : R_CONVT_X3_1411)
+                      : (pl.tl.id == 1 ? R_CONVT_LDS_2212 : R_CONVT_LDS_1411);
+    } else if (fused_t) {
+        pl.family = F_CONVT_REG;
+        const int64_t M = (int64_t)n * (in_h + 1) * (in_w + 1);
+        pl.grid = dim3((unsigned)smc::ceil_div(M, kConvTTile.bm), (unsigned)smc::ceil_div(cout, kConvTTile.bo),
+                       (unsigned)pl.nsplit);
+        pl.route = R_CONVT_GEMM_1411;
+    } else {
+        pl.grid = dim3((unsigned)smc::ceil_div(pl.max_m, c.bm), (unsigned)smc::ceil_div(cout, c.bo),
+                       (unsigned)(nphases * pl.nsplit));
+        bool scaled_ok = false;
+        // per-sample tiling pays where the per-sample weights are small next to the input planes (the
+        // high-resolution conv0 layers); on the 512-channel low-resolution layers writing n weight copies
+        // costs more than the register-staged kernel's in-loop scaling (tools/bench_gemm.py)
+        int taps_all = 0;
+        for (int i = 0; i < nphases; ++i) taps_all += phases[i].ntaps;
+        const bool small_w = (int64_t)taps_all * cout <= (int64_t)in_h * in_w;
+        const bool lds = lds_shape_ok(n, cin, cout, in_h, in_w, phases, nphases, c, &scaled_ok) &&
+                         (!has_s || scaled_ok || small_w);
+        if (lds) {
+            if (has_s && !scaled_ok) {
+                // per-sample tiling: grid.x = n x (tiles of the largest phase image)
+                int64_t tps = 0;
+                for (int i = 0; i < nphases; ++i)
+                    tps = std::max<int64_t>(tps, smc::ceil_div((int64_t)phases[i].out_h * phases[i].out_w, c.bm));
+                pl.grid.x = (unsigned)(tps * n);
+                pl.per_sample = true;
+            }
+            pl.wsample = has_s;
+            // XCD-aware tile order: one grid dimension, column tiles fastest (see conv_gemm_lds_kernel)
+            pl.ntn = (int)pl.grid.y;
+            pl.grid.x *= pl.grid.y;
+            pl.grid.y = 1;
+        }
+        const bool k32 = cin % 32 == 0;
+        if (lds && x3) {
+            pl.family = F_X3;
+            pl.x3 = tile == TILE_256x128 ? 2 : 1;
+            // Shared weights (no TAG), 128- and 64-channel tiles: waves that each own all of the tile's output
+            // channels (WO = 1: 128 x 32 or 64 x 32 per wave instead of 64 x 64 / 32 x 64), so a B fragment is split once
+            // per workgroup instead of once per wave pair, with 16-channel K steps (half the LDS per stage: 3 workgroups
+            // per CU instead of 2).  Measured against 32-channel steps (profiles/r05/ab5/, two interleaved rounds on one
+            // box): 468.96 / 467.66 against 467.77 / 466.56 images/s.
+            const bool wo1 = !tag && (tile == TILE_128x128 || tile == TILE_64x128);
+            // Elsewhere 32-channel K steps wherever the channels allow (two 16-channel chunks per barrier, the second's
+            // reads and split under the first's MFMAs; half the barriers per FLOP on the narrow tiles)
+            pl.bk = tile != TILE_256x128 && !wo1 && k32 ? 32 : 16;
+            pl.tag1 = tag && (tile == TILE_128x128 || tile == TILE_64x64);  // the other tiles have no TAG 1 form
+            const bool b32 = pl.bk == 32;
+            switch (tile) {
+            case TILE_256x128: pl.route = R_X3_WIDE; break;
+            case TILE_128x128: pl.route = wo1 ? R_X3_1441_16 : b32 ? R_X3_2222_32_T1 : R_X3_2222_16_T1; break;
+            case TILE_64x128: pl.route = wo1 ? R_X3_1421_16 : b32 ? R_X3_2212_32 : R_X3_2212_16; break;
+            case TILE_64x64: pl.route = pl.tag1 ? (b32 ? R_X3_2211_32_T1 : R_X3_2211_16_T1)
+                                                : (b32 ? R_X3_2211_32 : R_X3_2211_16); break;
+            case TILE_32x128: pl.route = b32 ? R_X3_1411_32 : R_X3_1411_16; break;
+            default: break;
+            }
+        } else if (lds && pl.nsplit == 1 && !pl.per_sample && (tile == TILE_32x128 || tile == TILE_64x128) &&
+                   row_ok(n, cin, cout, in_h, in_w, y_h, y_w, phases, nphases, Cfg{c.bo, 256}, &pl.rt)) {
+            // measured on MI355X (tools/bench_gemm.py, batch 4; tap-major kernel in brackets): 32 channels,
+            // 32 x 256 tiles of 8-channel steps: r = 1024 conv1 710 / 701 us fwd / data grad (840 / 818); 64
+            // channels, 64 x 256: r = 512 655 / 648 (688 / 679).  128+ channels stay tap-major (the 128 x 128
+            // row tile: 690 vs 634 us at r = 256).
+            pl.family = F_ROW;
+            pl.bk = 8;
+            pl.ntn = cout / c.bo;  // column tiles (a 96-channel data gradient: 3 x 32)
+            pl.grid = dim3((unsigned)((int)(((int64_t)n * in_h * in_w) / 256) * pl.ntn));
+            pl.route = tile == TILE_32x128 ? R_ROW_1412 : R_ROW_1422;
+        } else if (lds) {
+            pl.family = F_LDS;
+            // IR-SE50 (TAG 1) 64x64 tiles: 32-channel K steps (half the barriers of a 9-step split):
+            // f(4) + b(4) 3.57 -> 3.52 ms (profiles/r03_irse_bk32_ab.txt)
+            pl.bk = lds_bk32(tile, cin) || (tile == TILE_64x64 && k32 && tag) ? 32 : 16;
+            pl.tag1 = tag != 0;
+            const bool b32 = pl.bk == 32;
+            switch (tile) {
+            case TILE_128x128: pl.route = b32 ? (tag ? R_LDS_2222_32_T1 : R_LDS_2222_32)
+                                              : (tag ? R_LDS_2222_16_T1 : R_LDS_2222_16); break;
+            case TILE_64x64: pl.route = b32 ? R_LDS_2211_32_T1 : tag ? R_LDS_2211_16_T1 : R_LDS_2211_16; break;
+            case TILE_32x128: pl.route = tag ? R_LDS_1411_16_T1 : R_LDS_1411_16; break;
+            case TILE_64x128: pl.route = tag ? R_LDS_2212_16_T1 : R_LDS_2212_16; break;
+            default: break;  // the wide tile is split-bf16 only
+            }
+        } else {
+            // Register-staged kernel: the shapes the LDS-DMA kernel does not take (inputs of 2 GiB or more, style-scaled
+            // inputs whose tiles straddle images with large per-sample weights).  BK = 32 halves the barriers per FLOP;
+            // it pays on the long-K 512-channel layers, BK = 16 (more workgroups per CU: 32-40 KB LDS vs 64-80 KB) on
+            // the high-resolution ones (tools/bench_gemm.py).  Raw buffer loads need the input to fit a 32-bit byte
+            // offset, and only they have a TAG 1 form.
+            pl.family = F_REG;
+            pl.bk = k32 && cin >= 512 ? 32 : 16;
+            pl.buf = (int64_t)n * cin * in_h * in_w * 4 < (1LL << 31);
+            pl.tag1 = pl.buf && tag;
+#define SMC_PICK_REG(T)                                                                                     \
+    (pl.tag1 ? (pl.bk == 32 ? R_REG_##T##_32_BUF_T1 : R_REG_##T##_16_BUF_T1)                                \
+             : pl.bk == 32 ? (pl.buf ? R_REG_##T##_32_BUF : R_REG_##T##_32) : (pl.buf ? R_REG_##T##_16_BUF : R_REG_##T##_16))
+            switch (tile) {
+            case TILE_128x128: pl.route = SMC_PICK_REG(2222); break;
+            case TILE_32x128: pl.route = SMC_PICK_REG(1411); break;
+            case TILE_64x128: pl.route = SMC_PICK_REG(2212); break;
+            default: break;  // the small and wide tiles are taken only where lds_shape_ok holds for them
+            }
+#undef SMC_PICK_REG
+        }
     }
-    if (nsplit > 1) g_last_flags |= SMC_ROUTE_SPLIT_K;
-    if (prescale) {
-        g_last_flags |= SMC_ROUTE_PRESCALE;
-        // x * s after the split-K partials (the query reserved max(per-sample weights, prescaled input))
-        const int64_t part = nsplit > 1 ? ((nsplit * plane_elems * (int64_t)sizeof(float) + 255) / 256) * 256 : 0;
-        const int64_t need = part + pre_fl * (int64_t)sizeof(float);
-        SMC_CHECK(workspace && workspace_bytes >= need, "smc_conv_gemm_f32: workspace %lld < %lld bytes",
-                  (long long)workspace_bytes, (long long)need);
-        float* xs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + part);
-        const int64_t planes = (int64_t)n * cin, hw = (int64_t)in_h * in_w;
-        hipLaunchKernelGGL(xscale_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(planes * hw / 4, 256), 4096)),
-                           dim3(256), 0, smc::as_stream(stream), x, s_prescale, xs, hw, planes);
-        rc = smc::check_launch("smc_conv_gemm_f32 (prescaled input)");
-        if (rc != SMC_OK) return rc;
-        x = xs;
+    if (pl.wsample) pl.flags |= SMC_ROUTE_WSAMPLE;
+    if (pl.per_sample) pl.flags |= SMC_ROUTE_PER_SAMPLE;
+    return pl;
+}
+
+// ---- launch: one launcher per route, instantiated from the route list; the kernel's signature picks its operands
+template <auto K>
+void run_route(const Plan& pl, const GemmParams& p, hipStream_t st) {
+    using Fn = decltype(K);
+    if constexpr (std::is_same_v<Fn, void (*)(GemmParams)>)
+        hipLaunchKernelGGL(K, pl.grid, dim3(NT), 0, st, p);
+    else if constexpr (std::is_same_v<Fn, void (*)(GemmParams, RowTaps)>)
+        hipLaunchKernelGGL(K, pl.grid, dim3(NT), 0, st, p, pl.rt);
+    else if constexpr (std::is_same_v<Fn, void (*)(GemmParams, ConvTTaps)>)
+        hipLaunchKernelGGL(K, pl.grid, dim3(NT), 0, st, p, pl.ctt);
+    else {
+        static_assert(std::is_same_v<Fn, void (*)(GemmParams, ConvTParams)>, "a kernel signature without a launcher");
+        hipLaunchKernelGGL(K, pl.grid, dim3(NT), 0, st, p, pl.ctp);
     }
-    GemmParams p{};
-    p.x = x; p.n = n; p.cin = cin; p.in_h = in_h; p.in_w = in_w;
-    p.y = nsplit > 1 ? workspace : y;
-    p.cout = cout; p.y_h = y_h; p.y_w = y_w;
+}
+
+struct RouteRow {
+    const char* name;
+    void (*run)(const Plan&, const GemmParams&, hipStream_t);
+};
+constexpr RouteRow kRoutes[] = {
+    {"none", nullptr},
+#define SMC_ROUTE_ROW(id, kern, ...) {#kern "<" #__VA_ARGS__ ">", &run_route<kern<__VA_ARGS__>>},
+    SMC_ROUTES(SMC_ROUTE_ROW)
+#undef SMC_ROUTE_ROW
+};
+static_assert(sizeof(kRoutes) / sizeof(kRoutes[0]) == kRouteCount, "one row per route");
+
+// ---- prepare: the operands of a launch
+// The phases as the kernels read them (shared with smc::convt_up2_prepare).
+void fill_phases(GemmParams& p, const smc_conv_phase* phases, int nphases) {
     p.nphases = nphases;
-    int64_t max_m = 0;
     for (int i = 0; i < nphases; ++i) {
         const smc_conv_phase& q = phases[i];
         PhaseDev& d = p.ph[i];
@@ -2027,11 +2164,84 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
         d.wk = q.wk;
         d.wx3 = reinterpret_cast<const short*>(q.wk_x3);
         d.wx3_stride = 0;
-        const int64_t M = (int64_t)n * q.out_h * q.out_w;
-        if (M > max_m) max_m = M;
     }
-    SMC_CHECK(max_m < (1LL << 31), "smc_conv_gemm_f32: too many positions");
-    p.s = s_in;
+}
+
+// The per-sample weights W * s as split-bf16 planes at wp, [phase][n][planes of one sample], and the phases pointed
+// at them (shared with smc::convt_up2_prepare; the caller checks the launches).
+void launch_wsample_x3(GemmParams& p, int n, int cin, int cout, const smc_conv_phase* phases, int nphases,
+                       const float* s_in, short* wp, hipStream_t st) {
+    int64_t off = 0;
+    for (int i = 0; i < nphases; ++i) {
+        const int64_t per = (int64_t)phases[i].ntaps * cin * cout;
+        hipLaunchKernelGGL(x3_weights_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(per * n, 256), 4096)),
+                           dim3(256), 0, st, phases[i].wk, s_in, wp + off, phases[i].ntaps, cin, cout, n);
+        p.ph[i].wx3 = wp + off;
+        p.ph[i].wx3_stride = per * 3;
+        off += per * 3 * n;
+    }
+}
+
+// per-sample weights W[t][i][o] * s[n][i] at wsamp, [phase][n][taps*cin][cout]
+int make_wsample(GemmParams& p, int n, int cin, int cout, const smc_conv_phase* phases, int nphases,
+                 const float* s_in, float* wsamp, hipStream_t st) {
+    if (phases_x3(phases, nphases)) {
+        launch_wsample_x3(p, n, cin, cout, phases, nphases, s_in, reinterpret_cast<short*>(wsamp), st);
+        return smc::check_launch("smc_conv_gemm_f32 (per-sample split weights)");
+    }
+    int64_t off = 0;
+    for (int i = 0; i < nphases; ++i) {
+        const int rows = phases[i].ntaps * cin;
+        const int64_t tot4 = (int64_t)rows * cout / 4 * n;
+        hipLaunchKernelGGL(wscale_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(tot4, 256), 4096)),
+                           dim3(256), 0, st, phases[i].wk, s_in, wsamp + off, rows, cin, cout, n);
+        p.ph[i].wk = wsamp + off;
+        p.ph[i].wstride = (int64_t)rows * cout;
+        off += (int64_t)rows * cout * n;
+    }
+    return smc::check_launch("smc_conv_gemm_f32 (per-sample weights)");
+}
+
+// ---- plan, prepare, launch, finish
+int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y, int cout, int y_h, int y_w,
+                   const smc_conv_phase* phases, int nphases, const float* s_in, const smc_conv_epilogue* epi,
+                   float* workspace, int64_t workspace_bytes, void* stream, int tag) {
+    g_last_x3 = 0;
+    g_last_route = R_NONE;
+    g_last_flags = 0;
+    int rc = validate(x, n, cin, in_h, in_w, y, cout, y_h, y_w, phases, nphases);
+    if (rc != SMC_OK) return rc;
+    const Plan pl = plan_conv(x, n, cin, in_h, in_w, cout, y_h, y_w, phases, nphases, s_in != nullptr, epi, tag);
+    g_last_flags = pl.flags;
+    hipStream_t st = smc::as_stream(stream);
+    const int nsplit = pl.nsplit;
+    const int64_t plane_elems = (int64_t)n * cout * y_h * y_w;
+    // the workspace: the split-K partials, then the prescaled input or the per-sample weights (the query reserved the
+    // larger of the two)
+    const int64_t part = partials_offset(nsplit, plane_elems);
+    float* after_partials = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + part);
+    auto workspace_holds = [&](int64_t need) -> int {
+        SMC_CHECK(workspace && workspace_bytes >= need, "smc_conv_gemm_f32: workspace %lld < %lld bytes",
+                  (long long)workspace_bytes, (long long)need);
+        return SMC_OK;
+    };
+    if (nsplit > 1 && (rc = workspace_holds(nsplit * plane_elems * (int64_t)sizeof(float))) != SMC_OK) return rc;
+    if (pl.prescale) {
+        if ((rc = workspace_holds(part + pl.pre_fl * (int64_t)sizeof(float))) != SMC_OK) return rc;
+        const int64_t planes = (int64_t)n * cin, hw = (int64_t)in_h * in_w;
+        hipLaunchKernelGGL(xscale_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(planes * hw / 4, 256), 4096)),
+                           dim3(256), 0, st, x, s_in, after_partials, hw, planes);
+        rc = smc::check_launch("smc_conv_gemm_f32 (prescaled input)");
+        if (rc != SMC_OK) return rc;
+        x = after_partials;
+        s_in = nullptr;
+    }
+    GemmParams p{};
+    p.x = x; p.n = n; p.cin = cin; p.in_h = in_h; p.in_w = in_w;
+    p.y = nsplit > 1 ? workspace : y;
+    p.cout = cout; p.y_h = y_h; p.y_w = y_w;
+    fill_phases(p, phases, nphases);
+    SMC_CHECK(pl.max_m < (1LL << 31), "smc_conv_gemm_f32: too many positions");
     smc_conv_epilogue e{};
     e.mode = SMC_EPI_STORE; e.act = SMC_ACT_LINEAR; e.gain = 1.f; e.clamp = -1.f;
     if (epi) e = *epi;
@@ -2047,190 +2257,27 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
     SMC_CHECK(e.mode >= SMC_EPI_STORE && e.mode <= SMC_EPI_AFFINE, "smc_conv_gemm_f32: bad epilogue mode %d", e.mode);
     p.nsplit = nsplit;
     p.split_stride = plane_elems;
-
-    hipStream_t st = smc::as_stream(stream);
-    // per-sample weights W[t][i][o] * s[n][i], [phase][n][taps*cin][cout], after the split-K partials
-    auto make_wsample = [&]() -> int {
-        g_last_flags |= SMC_ROUTE_WSAMPLE;
-        const int64_t part = nsplit > 1 ? ((nsplit * plane_elems * (int64_t)sizeof(float) + 255) / 256) * 256 : 0;
-        const int64_t need = part + wsample_floats(n, cin, cout, phases, nphases) * (int64_t)sizeof(float);
-        SMC_CHECK(workspace && workspace_bytes >= need, "smc_conv_gemm_f32: workspace %lld < %lld bytes",
-                  (long long)workspace_bytes, (long long)need);
-        float* wsamp = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + part);
-        if (x3) {  // the per-sample weights W * s as split-bf16 planes, [phase][n][planes of one sample]
-            short* wp = reinterpret_cast<short*>(wsamp);
-            int64_t off = 0;
-            for (int i = 0; i < nphases; ++i) {
-                const int64_t per = (int64_t)phases[i].ntaps * cin * cout;
-                hipLaunchKernelGGL(x3_weights_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(per * n, 256), 4096)),
-                                   dim3(256), 0, st, phases[i].wk, s_in, wp + off, phases[i].ntaps, cin, cout, n);
-                p.ph[i].wx3 = wp + off;
-                p.ph[i].wx3_stride = per * 3;
-                off += per * 3 * n;
-            }
-            return smc::check_launch("smc_conv_gemm_f32 (per-sample split weights)");
-        }
-        int64_t off = 0;
-        for (int i = 0; i < nphases; ++i) {
-            const int rows = phases[i].ntaps * cin;
-            const int64_t tot4 = (int64_t)rows * cout / 4 * n;
-            hipLaunchKernelGGL(wscale_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(tot4, 256), 4096)),
-                               dim3(256), 0, st, phases[i].wk, s_in, wsamp + off, rows, cin, cout, n);
-            p.ph[i].wk = wsamp + off;
-            p.ph[i].wstride = (int64_t)rows * cout;
-            off += (int64_t)rows * cout * n;
-        }
-        return smc::check_launch("smc_conv_gemm_f32 (per-sample weights)");
-    };
-    if (convt_lds) {
-        if (s_in) {
-            rc = make_wsample();
-            if (rc != SMC_OK) return rc;
-        }
-        p.s = nullptr;
-        const int64_t hw_g = (int64_t)(in_h + 1) * (in_w + 1);
-        const int64_t mt = t_per_sample ? n * smc::ceil_div(hw_g, tl.bm) : smc::ceil_div(n * hw_g, tl.bm);
-        p.per_sample = t_per_sample ? 1 : 0;
-        if (t_per_sample) g_last_flags |= SMC_ROUTE_PER_SAMPLE;
-        p.ntn = cout / tl.bo;
-        dim3 g((unsigned)(mt * p.ntn), 1, (unsigned)nsplit);
-        g_last_x3 = x3 ? 1 : 0;
-        if (x3 && tl.id == 1 && SMC_X3_WO1) { g_last_route = R_CONVT_X3_1421; hipLaunchKernelGGL((convt_x3_kernel<1, 4, 2, 1>), g, dim3(NT), 0, st, p, ctt); }
-        else if (x3 && tl.id == 1) { g_last_route = R_CONVT_X3_2212; hipLaunchKernelGGL((convt_x3_kernel<2, 2, 1, 2>), g, dim3(NT), 0, st, p, ctt); }
-        else if (x3) { g_last_route = R_CONVT_X3_1411; hipLaunchKernelGGL((convt_x3_kernel<1, 4, 1, 1>), g, dim3(NT), 0, st, p, ctt); }
-        else if (tl.id == 1) { g_last_route = R_CONVT_LDS_2212; hipLaunchKernelGGL((convt_lds_kernel<2, 2, 1, 2, 16>), g, dim3(NT), 0, st, p, ctt); }
-        else { g_last_route = R_CONVT_LDS_1411; hipLaunchKernelGGL((convt_lds_kernel<1, 4, 1, 1, 16>), g, dim3(NT), 0, st, p, ctt); }
-        rc = smc::check_launch("smc_conv_gemm_f32 (fused transposed conv, LDS-DMA)");
-        if (rc != SMC_OK || nsplit == 1) return rc;
-        return smc_modconv_epilogue_f32(workspace, nsplit, plane_elems, y, n, cout, y_h, y_w, &e, stream);
+    p.per_sample = pl.per_sample ? 1 : 0;
+    p.ntn = pl.ntn;
+    p.s = pl.wsample ? nullptr : s_in;  // the kernels that take no per-sample weights scale in their K loop
+    if (pl.wsample) {
+        rc = workspace_holds(part + wsample_floats(n, cin, cout, phases, nphases) * (int64_t)sizeof(float));
+        if (rc != SMC_OK) return rc;
+        rc = make_wsample(p, n, cin, cout, phases, nphases, s_in, after_partials, st);
+        if (rc != SMC_OK) return rc;
     }
-    if (fused_t) {
-        const ConvTCfg tc = convt_cfg(cout);
-        const int64_t M = (int64_t)n * (in_h + 1) * (in_w + 1);
-        dim3 g((unsigned)smc::ceil_div(M, tc.bm), (unsigned)smc::ceil_div(cout, tc.bo), (unsigned)nsplit);
-        if (tc.id == 0) { g_last_route = R_CONVT_GEMM_2221; hipLaunchKernelGGL((convt_gemm_kernel<2, 2, 2, 1, 16>), g, dim3(NT), 0, st, p, ctp); }
-        else if (tc.id == 1) { g_last_route = R_CONVT_GEMM_1421; hipLaunchKernelGGL((convt_gemm_kernel<1, 4, 2, 1, 16>), g, dim3(NT), 0, st, p, ctp); }
-        else if (tc.id == 3) { g_last_route = R_CONVT_GEMM_1411; hipLaunchKernelGGL((convt_gemm_kernel<1, 4, 1, 1, 16>), g, dim3(NT), 0, st, p, ctp); }
-        else { g_last_route = R_CONVT_GEMM_1412; hipLaunchKernelGGL((convt_gemm_kernel<1, 4, 1, 2, 16>), g, dim3(NT), 0, st, p, ctp); }
-        rc = smc::check_launch("smc_conv_gemm_f32 (fused transposed conv)");
-        if (rc != SMC_OK || nsplit == 1) return rc;
-        return smc_modconv_epilogue_f32(workspace, nsplit, plane_elems, y, n, cout, y_h, y_w, &e, stream);
+    if (pl.route == R_NONE) {  // (a missing kernel is an error, never another kernel)
+        smc::set_error("smc_conv_gemm_f32: no kernel for this plan (family %d, tile %d)", (int)pl.family, (int)pl.tile);
+        return SMC_ERR_UNSUPPORTED;
     }
-    dim3 grid((unsigned)smc::ceil_div(max_m, c.bm), (unsigned)smc::ceil_div(cout, c.bo), (unsigned)(nphases * nsplit));
-    bool scaled_ok = false;
-    // per-sample tiling pays where the per-sample weights are small next to the input planes (the
-    // high-resolution conv0 layers); on the 512-channel low-resolution layers writing n weight copies
-    // costs more than the register-staged kernel's in-loop scaling (tools/bench_gemm.py)
-    int taps_all = 0;
-    for (int i = 0; i < nphases; ++i) taps_all += phases[i].ntaps;
-    const bool small_w = (int64_t)taps_all * cout <= (int64_t)in_h * in_w;
-    if (lds_shape_ok(n, cin, cout, in_h, in_w, phases, nphases, c, &scaled_ok) && (!s_in || scaled_ok || small_w)) {
-        if (s_in && !scaled_ok) {
-            // per-sample tiling: grid.x = n x (tiles of the largest phase image)
-            int64_t tps = 0;
-            for (int i = 0; i < nphases; ++i)
-                tps = std::max<int64_t>(tps, smc::ceil_div((int64_t)phases[i].out_h * phases[i].out_w, c.bm));
-            grid.x = (unsigned)(tps * n);
-            p.per_sample = 1;
-            g_last_flags |= SMC_ROUTE_PER_SAMPLE;
-        }
-        if (s_in) {
-            rc = make_wsample();
-            if (rc != SMC_OK) return rc;
-        }
-        p.s = nullptr;
-        // XCD-aware tile order: one grid dimension, column tiles fastest (see conv_gemm_lds_kernel)
-        p.ntn = (int)grid.y;
-        grid.x *= grid.y;
-        grid.y = 1;
-        RowTaps rt{};
-        if (x3) {
-            // 32-channel K steps wherever the channels allow (two 16-channel chunks per barrier, the second's reads and
-            // split under the first's MFMAs)
-            const bool k32 = cfg == 0 && cin % 32 == 0;
-            // 32-channel K steps for the narrow tiles too (A/B knob SMC_X3_K32_SMALL: half the barriers per FLOP)
-            const bool k32s = SMC_X3_K32_SMALL && cin % 32 == 0;
-            g_last_x3 = cfg == 6 ? 2 : 1;
-            if (cfg == 6) { g_last_route = R_X3_WIDE; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 8, 1, 16, 2, 0, true>), grid, dim3(NT), 0, st, p); }
-            else if (SMC_X3_WO1 && SMC_X3_WO1_K16 && cfg == 0 && !tag) { g_last_route = R_X3_1441_16; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 4, 1, 16>), grid, dim3(NT), 0, st, p); }
-            else if (SMC_X3_WO1 && SMC_X3_WO1_K16 && cfg == 5 && !tag) { g_last_route = R_X3_1421_16; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 2, 1, 16>), grid, dim3(NT), 0, st, p); }
-            else if (SMC_X3_WO1 && cfg == 0 && k32 && !tag) { g_last_route = R_X3_1441_32; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 4, 1, 32>), grid, dim3(NT), 0, st, p); }
-            else if (SMC_X3_WO1 && cfg == 5 && k32s && !tag) { g_last_route = R_X3_1421_32; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 2, 1, 32>), grid, dim3(NT), 0, st, p); }
-            else if (cfg == 0 && k32 && tag) { g_last_route = R_X3_2222_32_T1; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 2, 2, 32, SMC_X3_NST, 1>), grid, dim3(NT), 0, st, p); }
-            else if (cfg == 0 && k32) { g_last_route = R_X3_2222_32; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 2, 2, 32>), grid, dim3(NT), 0, st, p); }
-            else if (cfg == 0 && tag) { g_last_route = R_X3_2222_16_T1; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 2, 2, 16, SMC_X3_NST, 1>), grid, dim3(NT), 0, st, p); }
-            else if (cfg == 0) { g_last_route = R_X3_2222_16; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 2, 2, 16>), grid, dim3(NT), 0, st, p); }
-            else if (cfg == 3 && cin % 32 == 0 && tag)
-                { g_last_route = R_X3_2211_32_T1; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 1, 32, SMC_X3_NST, 1>), grid, dim3(NT), 0, st, p); }
-            else if (cfg == 3 && tag) { g_last_route = R_X3_2211_16_T1; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 1, 16, SMC_X3_NST, 1>), grid, dim3(NT), 0, st, p); }
-            else if (cfg == 3 && k32s) { g_last_route = R_X3_2211_32; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 1, 32>), grid, dim3(NT), 0, st, p); }
-            else if (cfg == 3) { g_last_route = R_X3_2211_16; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 1, 16>), grid, dim3(NT), 0, st, p); }
-            else if (cfg == 4 && k32s) { g_last_route = R_X3_1411_32; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 1, 1, 32>), grid, dim3(NT), 0, st, p); }
-            else if (cfg == 4) { g_last_route = R_X3_1411_16; hipLaunchKernelGGL((conv_gemm_x3_kernel<1, 4, 1, 1, 16>), grid, dim3(NT), 0, st, p); }
-            else if (k32s) { g_last_route = R_X3_2212_32; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 2, 32>), grid, dim3(NT), 0, st, p); }
-            else { g_last_route = R_X3_2212_16; hipLaunchKernelGGL((conv_gemm_x3_kernel<2, 2, 1, 2, 16>), grid, dim3(NT), 0, st, p); }
-            rc = smc::check_launch("smc_conv_gemm_f32 (split-bf16)");
-            if (rc != SMC_OK || nsplit == 1) return rc;
-            return smc_modconv_epilogue_f32(workspace, nsplit, plane_elems, y, n, cout, y_h, y_w, &e, stream);
-        }
-        if (nsplit == 1 && !p.per_sample && (cfg == 4 || cfg == 5) &&
-            row_ok(n, cin, cout, in_h, in_w, y_h, y_w, phases, nphases, Cfg{c.bo, 256}, &rt)) {
-            p.ntn = cout / c.bo;  // column tiles (a 96-channel data gradient: 3 x 32)
-            // measured on MI355X (tools/bench_gemm.py, batch 4; tap-major kernel in brackets): 32 channels,
-            // 32 x 256 tiles of 8-channel steps: r = 1024 conv1 710 / 701 us fwd / data grad (840 / 818); 64
-            // channels, 64 x 256: r = 512 655 / 648 (688 / 679).  128+ channels stay tap-major (the 128 x 128
-            // row tile: 690 vs 634 us at r = 256).
-            const int tiles = (int)(((int64_t)n * in_h * in_w) / 256) * p.ntn;
-            if (cfg == 4) { g_last_route = R_ROW_1412; hipLaunchKernelGGL((conv_row_kernel<1, 4, 1, 2, 8>), dim3(tiles), dim3(NT), 0, st, p, rt); }
-            else { g_last_route = R_ROW_1422; hipLaunchKernelGGL((conv_row_kernel<1, 4, 2, 2, 8>), dim3(tiles), dim3(NT), 0, st, p, rt); }
-            return smc::check_launch("smc_conv_gemm_f32 (row-halo)");
-        }
-#define SMC_LAUNCH_LDS(WO_, WM_, TO_, TM_)                                                                          \
-    do {                                                                                                          \
-        if (tag) { g_last_route = R_LDS_##WO_##WM_##TO_##TM_##_16_T1; hipLaunchKernelGGL((conv_gemm_lds_kernel<WO_, WM_, TO_, TM_, 16, 2, 1>), grid, dim3(NT), 0, st, p); } \
-        else { g_last_route = R_LDS_##WO_##WM_##TO_##TM_##_16; hipLaunchKernelGGL((conv_gemm_lds_kernel<WO_, WM_, TO_, TM_, 16, 2>), grid, dim3(NT), 0, st, p); } \
-    } while (0)
-        if (cfg == 0 && lds_bk32(cfg, cin) && tag)
-            { g_last_route = R_LDS_2222_32_T1; hipLaunchKernelGGL((conv_gemm_lds_kernel<2, 2, 2, 2, 32, 2, 1>), grid, dim3(NT), 0, st, p); }
-        else if (cfg == 0 && lds_bk32(cfg, cin))
-            { g_last_route = R_LDS_2222_32; hipLaunchKernelGGL((conv_gemm_lds_kernel<2, 2, 2, 2, 32, 2>), grid, dim3(NT), 0, st, p); }
-        else if (cfg == 0) SMC_LAUNCH_LDS(2, 2, 2, 2);
-        // IR-SE50 (TAG 1) 64x64 tiles: 32-channel K steps (half the barriers of a 9-step split):
-        // f(4) + b(4) 3.57 -> 3.52 ms (profiles/r03_irse_bk32_ab.txt)
-        else if (cfg == 3 && cin % 32 == 0 && tag)
-            { g_last_route = R_LDS_2211_32_T1; hipLaunchKernelGGL((conv_gemm_lds_kernel<2, 2, 1, 1, 32, 2, 1>), grid, dim3(NT), 0, st, p); }
-        else if (cfg == 3) SMC_LAUNCH_LDS(2, 2, 1, 1);
-        else if (cfg == 4) SMC_LAUNCH_LDS(1, 4, 1, 1);
-        else SMC_LAUNCH_LDS(2, 2, 1, 2);
-#undef SMC_LAUNCH_LDS
-        rc = smc::check_launch("smc_conv_gemm_f32 (LDS-DMA)");
-        if (rc != SMC_OK || nsplit == 1) return rc;
-        return smc_modconv_epilogue_f32(workspace, nsplit, plane_elems, y, n, cout, y_h, y_w, &e, stream);
-    }
-    // Register-staged kernel: the shapes the LDS-DMA kernel does not take (inputs of 2 GiB or more, style-scaled
-    // inputs whose tiles straddle images with large per-sample weights).  BK = 32 halves the barriers per FLOP; it
-    // pays on the long-K 512-channel layers, BK = 16 (more workgroups per CU: 32-40 KB LDS vs 64-80 KB) on the
-    // high-resolution ones (tools/bench_gemm.py).  Raw buffer loads need the input to fit a 32-bit byte offset.
-    const bool k32 = cin % 32 == 0 && cin >= 512;
-    const bool buf = (int64_t)n * cin * in_h * in_w * 4 < (1LL << 31);
-#define SMC_LAUNCH(WO_, WM_, TO_, TM_)                                                                       \
-    do {                                                                                                   \
-        if (k32 && buf && tag) { g_last_route = R_REG_##WO_##WM_##TO_##TM_##_32_BUF_T1; hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 32, true, 1>), grid, dim3(NT), 0, st, p); } \
-        else if (buf && tag) { g_last_route = R_REG_##WO_##WM_##TO_##TM_##_16_BUF_T1; hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 16, true, 1>), grid, dim3(NT), 0, st, p); } \
-        else if (k32 && buf) { g_last_route = R_REG_##WO_##WM_##TO_##TM_##_32_BUF; hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 32, true>), grid, dim3(NT), 0, st, p); }   \
-        else if (k32) { g_last_route = R_REG_##WO_##WM_##TO_##TM_##_32; hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 32, false>), grid, dim3(NT), 0, st, p); }    \
-        else if (buf) { g_last_route = R_REG_##WO_##WM_##TO_##TM_##_16_BUF; hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 16, true>), grid, dim3(NT), 0, st, p); }     \
-        else { g_last_route = R_REG_##WO_##WM_##TO_##TM_##_16; hipLaunchKernelGGL((conv_gemm_kernel<WO_, WM_, TO_, TM_, 16, false>), grid, dim3(NT), 0, st, p); }             \
-    } while (0)
-    if (cfg == 0) SMC_LAUNCH(2, 2, 2, 2);
-    else if (cfg == 4) SMC_LAUNCH(1, 4, 1, 1);
-    else if (cfg == 5) SMC_LAUNCH(2, 2, 1, 2);
-    else SMC_LAUNCH(2, 2, 1, 1);
-#undef SMC_LAUNCH
-    rc = smc::check_launch("smc_conv_gemm_f32");
+    g_last_x3 = pl.x3;
+    g_last_route = pl.route;
+    kRoutes[pl.route].run(pl, p, st);
+    rc = smc::check_launch(kFamilyWhat[pl.family]);
     if (rc != SMC_OK || nsplit == 1) return rc;
     return smc_modconv_epilogue_f32(workspace, nsplit, plane_elems, y, n, cout, y_h, y_w, &e, stream);
 }
+
 
 }  // namespace
 
@@ -2243,7 +2290,7 @@ SMC_API int smc_conv_gemm_last_route_flags(void) { return g_last_flags; }
 SMC_API int smc_conv_gemm_route_count(void) { return kRouteCount; }
 
 SMC_API const char* smc_conv_gemm_route_name(int route) {
-    return route >= 0 && route < kRouteCount ? kRouteNames[route] : nullptr;
+    return route >= 0 && route < kRouteCount ? kRoutes[route].name : nullptr;
 }
 
 SMC_API int64_t smc_conv_weights_x3_bytes(int ntaps, int cin, int cout) {
@@ -2315,29 +2362,13 @@ int convt_up2_prepare(const float* x, int n, int cin, int h, int w, float* y, in
     GemmParams& p = *pp;
     p.x = x; p.n = n; p.cin = cin; p.in_h = h; p.in_w = w;
     p.cout = cout; p.y_h = th; p.y_w = tw;
-    p.nphases = nphases;
-    for (int i = 0; i < nphases; ++i) {
-        p.ph[i].ntaps = phases[i].ntaps;
-        p.ph[i].wk = phases[i].wk;
-        p.ph[i].wx3 = reinterpret_cast<const short*>(phases[i].wk_x3);
-        p.ph[i].wx3_stride = 0;
-    }
+    fill_phases(p, phases, nphases);
     if (!s_in) return SMC_OK;
-    // the per-sample weights W * s as split-bf16 planes, [phase][n][planes of one sample] (as conv_gemm_impl)
     const int64_t need = wsample_floats(n, cin, cout, phases, nphases) * (int64_t)sizeof(float);
     SMC_CHECK(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
               "smc_modconv_up2_f32: workspace %lld < %lld bytes (or not 16-B aligned)", (long long)workspace_bytes,
               (long long)need);
-    short* wp = reinterpret_cast<short*>(workspace);
-    int64_t off = 0;
-    for (int i = 0; i < nphases; ++i) {
-        const int64_t per = (int64_t)phases[i].ntaps * cin * cout;
-        hipLaunchKernelGGL(x3_weights_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(per * n, 256), 4096)), dim3(256),
-                           0, as_stream(stream), phases[i].wk, s_in, wp + off, phases[i].ntaps, cin, cout, n);
-        p.ph[i].wx3 = wp + off;
-        p.ph[i].wx3_stride = per * 3;
-        off += per * 3 * n;
-    }
+    launch_wsample_x3(p, n, cin, cout, phases, nphases, s_in, reinterpret_cast<short*>(workspace), as_stream(stream));
     return check_launch("smc_modconv_up2_f32 (per-sample split weights)");
 }
 }  // namespace smc

@@ -96,3 +96,29 @@ def test_dd_workspace_queries_without_gpu():
     rc = lib.smc_modconv_blur_act_bwd_f32(fake, fake, fake, fake, 2, 8, 128, 128, 129, 129, 0, fake, 4, 4, 2, 2, 4.0, 1,
                                           ctypes.byref(epi), fake, 16, None)
     assert rc == 1 and b"workspace" in lib.smc_last_error()
+
+
+def _check_route_names(count, name_of, expected):
+    names = [name_of(r) for r in range(count)]
+    assert names[0] == b"none" and name_of(-1) is None and name_of(count) is None
+    assert len(set(names)) == len(names), "route names are the identity of a route: no two alike"
+    got = {n.decode() for n in names[1:]}
+    assert got == expected, (sorted(got - expected), sorted(expected - got))
+
+
+def test_route_tables_hold_only_tested_routes():
+    """The dispatchers' route tables are host data (no device call).  Every name in them is a route that a case of the
+    GPU route tests is built to reach (EXPECTED) or one of the few those tests waive with a test of their own (the
+    2 GiB inputs; the split-bf16 Winograd kernel that is off by default) -- so no instantiation that nothing can launch
+    is compiled into the library, and no tested route has left it."""
+    from tests import conv_cases, wino_cases
+    from tests.test_gpu_conv_routes import WAIVED as conv_waived
+    from tests.test_gpu_wino_routes import WAIVED as wino_waived
+    lib = _hip.load()
+    expected = {name for forms in conv_cases.EXPECTED.values() for name, _ in forms} | set(conv_waived)
+    _check_route_names(lib.smc_conv_gemm_route_count(), lib.smc_conv_gemm_route_name, expected)
+    for fam, count, name_of in ((2, lib.smc_conv3x3_wino_route_count(), lib.smc_conv3x3_wino_route_name),
+                                (4, lib.smc_conv3x3_wino4_route_count(), lib.smc_conv3x3_wino4_route_name)):
+        expected = {wino_cases.EXPECTED[c.id][0] for c in wino_cases.CASES if c.fam == fam}
+        expected |= {k for k in wino_waived if k.startswith("wino4_") == (fam == 4)}
+        _check_route_names(count, name_of, expected)

@@ -22,32 +22,12 @@ DEV = cc.DEV
 FLAG_NAMES = {SPLIT_K: "split-K", PER_SAMPLE: "per-sample tiling", PRESCALE: "prescaled input",
               WSAMPLE: "per-sample weights"}
 
-# Routes no table case has to reach.  Only two reasons are admissible:
+# Routes no table case has to reach.  One reason is admissible:
 #  (a) the guard contains "input >= 2 GiB" -- all six run in test_2gib_routes / test_gpu_ops.test_conv_gemm_2gib_input_fallback
-#      against the fast routes on half batches;
-#  (b) the launch is unreachable with the default compile-time knobs (SMC_X3_WO1 = SMC_X3_WO1_K16 = 1): the entry quotes
-#      the earlier branch that shadows it (DESIGN.md section 3 lists them under the product-trimming note).
-_WO1_0 = "shadowed by `SMC_X3_WO1 && SMC_X3_WO1_K16 && cfg == 0 && !tag` (conv_gemm_x3_kernel<1,4,4,1,16>) two branches up"
-_WO1_5 = "shadowed by `SMC_X3_WO1 && SMC_X3_WO1_K16 && cfg == 5 && !tag` (conv_gemm_x3_kernel<1,4,2,1,16>) two branches up"
-_CFG3 = ("(b) cfg == 3 is set only where small_tile_ok() holds, which repeats the LDS-DMA guard `lds_shape_ok(..., "
-         "Cfg{64, 64}, &scaled_ok) && (!has_s || scaled_ok || taps_all * cout <= in_h * in_w)`: the LDS-DMA branch takes "
-         "every cfg == 3 call before the register-staged `else SMC_LAUNCH(2, 2, 1, 1)`")
+#      against the fast routes on half batches.
+# (The dispatcher's route table holds no unreachable instantiation: tests/test_capi.py compares its names with this set.)
 _GIB = "(a) `buf = n * cin * in_h * in_w * 4 < 2^31` false: input >= 2 GiB"
 WAIVED = {
-    "convt_x3_kernel<2,2,1,2>": "(b) shadowed by `x3 && tl.id == 1 && SMC_X3_WO1` (convt_x3_kernel<1,4,2,1>) one branch up",
-    "convt_gemm_kernel<2,2,2,1,16>": "(b) convt_fusable() requires cout <= 32, convt_cfg(cout).id == 0 requires cout % 128 == 0",
-    "convt_gemm_kernel<1,4,2,1,16>": "(b) convt_fusable() requires cout <= 32, convt_cfg(cout).id == 1 requires cout % 64 == 0",
-    "convt_gemm_kernel<1,4,1,2,16>": "(b) convt_cfg() returns id 0, 1 or 3 only: the final `else` has no caller",
-    "conv_gemm_x3_kernel<1,4,4,1,32>": "(b) " + _WO1_0,
-    "conv_gemm_x3_kernel<2,2,2,2,32>": "(b) " + _WO1_0 + " (tag 0; tag 1 takes the <...,NST,1> branch above it)",
-    "conv_gemm_x3_kernel<2,2,2,2,16>": "(b) " + _WO1_0 + " (tag 0; tag 1 takes the <...,NST,1> branch above it)",
-    "conv_gemm_x3_kernel<1,4,2,1,32>": "(b) " + _WO1_5,
-    "conv_gemm_kernel<2,2,1,1,32,true,1>": _CFG3,
-    "conv_gemm_kernel<2,2,1,1,16,true,1>": _CFG3,
-    "conv_gemm_kernel<2,2,1,1,32,true>": _CFG3,
-    "conv_gemm_kernel<2,2,1,1,32,false>": _CFG3,
-    "conv_gemm_kernel<2,2,1,1,16,true>": _CFG3,
-    "conv_gemm_kernel<2,2,1,1,16,false>": _CFG3,
     # (a): covered by the 2 GiB tests, not by a table case
     "conv_gemm_kernel<1,4,1,1,16,false>": _GIB + " (test_gpu_ops.test_conv_gemm_2gib_input_fallback asserts it)",
     "conv_gemm_kernel<1,4,1,1,32,false>": _GIB + " (test_2gib_routes[cin512-cout32])",

@@ -43,7 +43,7 @@ def _check(got, x64, w64, what):
 
 
 # n, cin, cout, h, w  (non-square, 512 channels, cin != cout).  Block shapes: TC 16 at w = 32 only, TC 32 at every
-# other width (wino_tc() with SMC_WINO_TC_MAX 32 never picks 64 tile columns; tests/test_gpu_wino_routes.py holds the
+# other width (wino_tc() never picks 64 tile columns; tests/test_gpu_wino_routes.py holds the
 # cases per block shape and asserts the kernel each one ran)
 SHAPES = [
     (2, 32, 32, 32, 32),
@@ -242,7 +242,7 @@ def test_wino_unsupported_shapes():
     assert rc == 2 and b"Winograd" in lib.smc_last_error()
 
 
-# The split-bf16 F(2x2) kernel (wino.hip wino_x3_kernel) is off in the product; these tests switch it on
+# The split-bf16 F(2x2) kernel (wino.hip wino_x3r_kernel) is off in the product; these tests switch it on
 # (smc_set_wino_x3) around each check.
 X3_SHAPES = [  # cin = cout = 32 with 2 x 32 tile blocks (w % 64 == 0, h % 4 == 0): the split-bf16 kernel
     (2, 32, 32, 64, 64),
@@ -288,7 +288,7 @@ def _rows_check(got, x64, w64, what, rows=None):
 
 @pytest.mark.parametrize("shape", X3_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_wino_x3_vs_fp64(shape, x3_mode):
-    """The split-bf16 F(2x2) kernel (wino_x3_kernel, taken by the conv1 forward's MODACT form): the style-scaled
+    """The split-bf16 F(2x2) kernel (wino_x3r_kernel, taken by the conv1 forward's MODACT form): the style-scaled
     forward (s folded into per-image planes) and a data-gradient-shaped call (flipped taps, one plane set), through that
     form with d = 1, no noise, no bias, lrelu slope 1, gain 1 and an unreachable clamp (y = the conv exactly), against
     fp64 at the fp32 kernel's tolerance TOL -- the three-term products leave out <= 2^-23 |u v| each."""

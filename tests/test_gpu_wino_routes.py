@@ -21,17 +21,11 @@ from tests import wino_cases as wc
 
 pytestmark = pytest.mark.gpu
 
-# Routes no table case has to reach.  Only two reasons are admissible:
-#  (a) the route is off by default and asserted by an existing test that enables it;
-#  (b) the launch is unreachable with the default compile-time knobs: the entry quotes the guard that shadows it.
-_TC64 = ("(b) `#define SMC_WINO_TC_MAX 32`: wino_tc()'s `for (int tc = SMC_WINO_TC_MAX; tc >= 16; tc /= 2)` never "
-         "returns 64, so launch_wino_tc's `if (tc == 64)` is never taken")
+# Routes no table case has to reach.  One reason is admissible:
+#  (a) the route is off by default and asserted by an existing test that enables it.
 _X3 = ("(a) `wino_x3_bytes() > 0` needs `g_wino_x3` != 0 (smc_set_wino_x3, 0 by default): asserted by "
        "test_gpu_wino.test_wino_x3_vs_fp64 and test_wino_x3_modact_vs_fp32_kernel, which enable it")
-_X3_LDS = "(b) `#define SMC_WINO_X3R 1`: launch_wino_x3's `if (SMC_WINO_X3R)` takes wino_x3r_kernel"
-WAIVED = {f"wino_kernel<64,{sm},{ek}>": _TC64 for sm in (1, 2) for ek in (0, 1, 2, 3)}
-WAIVED.update({"wino_x3r_kernel<1>": _X3, "wino_x3r_kernel<2>": _X3,
-               "wino_x3_kernel<1>": _X3_LDS, "wino_x3_kernel<2>": _X3_LDS})
+WAIVED = {"wino_x3r_kernel<1>": _X3, "wino_x3r_kernel<2>": _X3}
 
 FLAG_NAMES = {wc.SPLIT: "split-K", wc.FOLD: "style folded into U"}
 

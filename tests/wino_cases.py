@@ -11,8 +11,8 @@ A case is (id, fam, n, cin, cout, h, w, epi, style, flip, ws):
   flip      1: the taps of the data gradient (smc_wino*_weights_f32 flip = 1 of a [cin][cout][3][3] forward weight)
   ws        F(2x2) only: the call passes the workspace smc_conv3x3_wino_workspace_size() asks for
 
-The guards the routes are read off (wino.hip; SMC_WINO_TC_MAX 32, SMC_WINO_FOLD 1, split target 512):
-  TC     wino_tc(): `for (tc = SMC_WINO_TC_MAX; tc >= 16; tc /= 2) if ((w / 2) % tc == 0 && (h / 2) % (WBT / tc) == 0)`
+The guards the routes are read off (wino.hip; SMC_WINO_FOLD 1, split target 512):
+  TC     wino_tc(): `for (tc = 32; tc >= 16; tc /= 2) if ((w / 2) % tc == 0 && (h / 2) % (WBT / tc) == 0)`
          -> 32 where w % 64 == 0 and h % 4 == 0, else 16 where w % 32 == 0 and h % 8 == 0 (so TC 16 means w % 64 == 32)
   fold   `if (SMC_WINO_FOLD && s_in && fold_bytes > 0 && ws_ok)`, fold_bytes > 0 iff cin * cout <= 128 * 128: the
          launch then runs SM = 2 (`s_in = nullptr`) with SMC_ROUTE_WINO_FOLD
@@ -145,7 +145,7 @@ for _key, _g, _n, _cin, _cout, _gi, _epi, _style, (_sm, _fl), _ns in _SPLIT_ROWS
     CASES.append(_c)
     EXPECTED[_c.id] = (f"wino_kernel<{_g[2:]},{_sm},3>", _fl, _ns)
 
-# w = 128: two 32-column blocks per tile row -- and the width a build with SMC_WINO_TC_MAX = 64 would run as one
+# w = 128: two 32-column blocks per tile row -- and the width a wino_tc() that offered 64 columns would run as one
 # 64-column block (`(w / 2) % 64 == 0`), so that knob cannot change without this case's route assertion failing
 CASES.append(Case("tc32_store_w128", 2, 1, 16, 32, 4, 128, "store", False, 0, False))
 EXPECTED["tc32_store_w128"] = ("wino_kernel<32,2,0>", 0, 1)
