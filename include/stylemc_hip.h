@@ -591,6 +591,49 @@ int smc_irse_forward_f32(const smc_irse_net* net, const float* img, int n, float
 int smc_irse_backward_f32(const smc_irse_net* net, const float* dfeat, int n_saved, int n, const float* saved,
                           float* dimg, float* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * e4e / pSp encoder (encoder4editing/models/encoders/psp_encoders.py:58-200, helpers.py:123-140): the IR-SE50 trunk
+ * with feature taps, the FPN's upsample-add and the grouped stride-2 convolution of the 18 map2style heads.
+ * Inference only, fp32.  Added under ABI version 6 without a version bump: callers detect these entry points by symbol.
+ *
+ * smc_irse_trunk_f32 runs the stem and the units of a net exactly as smc_irse_forward_f32 does (nothing saved), without
+ * the output layer: feat, flat and the fc_* fields are not read and may be 0 / NULL (the adjoint phases are still
+ * sized for the workspace and must be described).  The outputs of the units tap_units[0 .. ntaps) (1 <= ntaps <= 3,
+ * ascending, host array) are written to the caller's buffers tap_out[t] (host array of device pointers), each
+ * [n][depth][in_h/s][in_w/s] of that unit.  e4e taps units 6, 20 and 23 (psp_encoders.py:177-184).
+ */
+int64_t smc_irse_trunk_workspace_bytes(const smc_irse_net* net, int n);
+int smc_irse_trunk_f32(const smc_irse_net* net, const float* img, int n, const int* tap_units, float* const* tap_out,
+                       int ntaps, float* workspace, int64_t workspace_bytes, void* stream);
+
+/* y = bilinear(x -> out_h x out_w, align_corners = True) + lat  (helpers.py:123-140 _upsample_add):
+ * x [planes][in_h][in_w], lat and y [planes][out_h][out_w]; any sizes >= 1, every tensor below 2 GiB. */
+int smc_upsample_add_f32(const float* x, int64_t planes, int in_h, int in_w, const float* lat, float* y, int out_h,
+                         int out_w, void* stream);
+
+/* `groups` independent 3x3 stride-2 pad-1 convolutions in one launch (GradualStyleBlock, psp_encoders.py:41-47):
+ *   y[g][s][o][a][b] = lrelu(bias[g][o] + sum_{t < ntaps, i < cin} wk[g][t][i][o] * x_g[s][i][2a - 1 + ky_t][2b - 1 + kx_t],
+ *                            alpha)
+ * with out = (in - 1) / 2 + 1 for any h, w >= 1 (odd, non-square and 1 x 1 planes included), reads outside the plane 0,
+ * lrelu(z, alpha) = z > 0 ? z : alpha z (alpha 0.01: nn.LeakyReLU(); alpha 1: linear).
+ *   x_g[s] = x + g * x_group_stride + s * x_sample_stride (floats), a contiguous [cin][h][w] block: group stride 0 lets
+ *     every group read the same feature map, and strides of a wider tensor select channel slices of it.
+ *   taps: host array of the ntaps (1..9) taps summed, each ky*3 + kx, ascending; wk [groups][ntaps][cin][cout] holds
+ *     only those.  The caller drops the taps that can only touch padding at this plane size (2x2 -> 1x1 keeps 4,
+ *     1x1 -> 1x1 keeps the centre: with alpha = 1 that is a grouped Linear, the heads' EqualLinear).
+ *   bias [groups][cout], may be NULL.  y [groups][n][cout][oh][ow].
+ * Per group a GEMM on the exact-fp32 MFMA (M = n*oh*ow, N = cout, K = ntaps*cin).  Where tiles x groups cannot fill
+ * the chip, K is split across workgroups into partial planes in `workspace` (smc_conv_s2_grouped_workspace_size()
+ * bytes, 0: no split; -1: unsupported shape) that a second kernel sums in split order: no atomics, bit-identical from
+ * run to run.  Limits (smc_conv_s2_grouped_supported(); otherwise SMC_ERR_INVALID from host-side validation, before
+ * any launch): 1 <= groups <= 65535, cin % 16 == 0, cout % 32 == 0, groups*n*cin*h*w, groups*n*cout*oh*ow and
+ * groups*9*cin*cout floats each below 2 GiB, the strided input span below 2 GiB, wk 16-byte aligned. */
+int smc_conv_s2_grouped_supported(int groups, int n, int cin, int cout, int h, int w);
+int64_t smc_conv_s2_grouped_workspace_size(int groups, int n, int cin, int cout, int h, int w, int ntaps);
+int smc_conv_s2_grouped_f32(const float* x, int64_t x_sample_stride, int64_t x_group_stride, int groups, int n, int cin,
+                            int h, int w, const float* wk, const int* taps, int ntaps, const float* bias, float alpha,
+                            float* y, int cout, float* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,13 @@ _SIGS = {
     "smc_irse_workspace_bytes": (c_int64, [P, c_int]),
     "smc_irse_forward_f32": (c_int, [P, P, c_int, P, P, P, c_int64, P]),
     "smc_irse_backward_f32": (c_int, [P, P, c_int, c_int, P, P, P, c_int64, P]),
+    "smc_irse_trunk_workspace_bytes": (c_int64, [P, c_int]),
+    "smc_irse_trunk_f32": (c_int, [P, P, c_int, P, P, c_int, P, c_int64, P]),
+    "smc_upsample_add_f32": (c_int, [P, c_int64, c_int, c_int, P, P, c_int, c_int, P]),
+    "smc_conv_s2_grouped_supported": (c_int, [c_int] * 6),
+    "smc_conv_s2_grouped_workspace_size": (c_int64, [c_int] * 7),
+    "smc_conv_s2_grouped_f32": (c_int, [P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P,
+                                        c_float, P, c_int, P, c_int64, P]),
 }
 
 _lib = None

@@ -324,6 +324,7 @@ int64_t conv_ws_need(const smc_irse_net& net, int n) {
             q(u.depth, u.cin, oh, ow, &u.sc_bwd, 1);
         }
     }
+    if (!net.fc_wt) return m;  // trunk only (smc_irse_trunk_f32): no output layer
     const int64_t lin = std::max(smc_linear_workspace_size(n, net.feat, net.flat),
                                  smc_linear_workspace_size(n, net.flat, net.feat));
     return std::max(m, lin);
@@ -357,10 +358,10 @@ int64_t ws_floats(const smc_irse_net& net, int n, float* base, Ws* w) {
     return off;
 }
 
-int net_validate(const smc_irse_net* net, int n) {
+// stem and units (everything the trunk runs); net_validate adds the output layer
+int trunk_validate(const smc_irse_net* net, int n) {
     SMC_CHECK(net && net->units && net->n_units >= 1 && n >= 1, "smc_irse: bad net / batch");
     SMC_CHECK(net->stem_cin >= net->img_ch && net->stem_cin % 16 == 0, "smc_irse: stem_cin must pad img_ch to 16k");
-    SMC_CHECK(net->fc_wt && net->fc_w && net->flat % 32 == 0 && net->feat % 32 == 0, "smc_irse: bad output layer");
     for (int k = 0; k < net->n_units; ++k) {
         const smc_irse_unit& u = net->units[k];
         SMC_CHECK(u.stride == 1 || u.stride == 2, "smc_irse: unit %d stride %d", k, u.stride);
@@ -372,6 +373,13 @@ int net_validate(const smc_irse_net* net, int n) {
         SMC_CHECK(u.sc_conv || u.cin == u.depth, "smc_irse: unit %d identity shortcut needs cin == depth", k);
         SMC_CHECK(u.c2_bwd_nphases == (u.stride == 2 ? 4 : 1), "smc_irse: unit %d adjoint phases", k);
     }
+    return SMC_OK;
+}
+
+int net_validate(const smc_irse_net* net, int n) {
+    const int rc = trunk_validate(net, n);
+    if (rc != SMC_OK) return rc;
+    SMC_CHECK(net->fc_wt && net->fc_w && net->flat % 32 == 0 && net->feat % 32 == 0, "smc_irse: bad output layer");
     const smc_irse_unit& last = net->units[net->n_units - 1];
     SMC_CHECK((int64_t)last.depth * unit_out_hw(last) == net->flat, "smc_irse: flat %d mismatch", net->flat);
     return SMC_OK;
@@ -392,27 +400,11 @@ smc_conv_epilogue epi_mode(int mode) {
         if (rc_ != SMC_OK) return rc_; \
     } while (0)
 
-}  // namespace
-
-SMC_API int64_t smc_irse_saved_floats(const smc_irse_net* net, int n) {
-    if (net_validate(net, n) != SMC_OK) return -1;
-    return saved_floats(*net, n, nullptr, nullptr, nullptr);
-}
-
-SMC_API int64_t smc_irse_workspace_bytes(const smc_irse_net* net, int n) {
-    if (net_validate(net, n) != SMC_OK) return -1;
-    return ws_floats(*net, n, nullptr, nullptr) * (int64_t)sizeof(float);
-}
-
-SMC_API int smc_irse_forward_f32(const smc_irse_net* net, const float* img, int n, float* feat, float* saved,
-                                 float* workspace, int64_t workspace_bytes, void* stream) {
-    SMC_TRY(net_validate(net, n));
-    SMC_CHECK(img && feat && workspace, "smc_irse_forward_f32: null pointer");
-    SMC_CHECK(workspace_bytes >= ws_floats(*net, n, nullptr, nullptr) * (int64_t)sizeof(float),
-              "smc_irse_forward_f32: workspace too small");
+// Stem and units of the forward (shared by smc_irse_forward_f32 and smc_irse_trunk_f32); *x_out = the last unit's
+// output.  The outputs of the units tap_units[0 .. ntaps) go to tap_out[.] instead of a workspace buffer.
+int forward_body(const smc_irse_net* net, const float* img, int n, float* saved, const Ws& w, void* stream,
+                 const int* tap_units, float* const* tap_out, int ntaps, float** x_out) {
     hipStream_t st = smc::as_stream(stream);
-    Ws w;
-    ws_floats(*net, n, workspace, &w);
     std::vector<UnitS> us(net->n_units);
     float* stem_z = nullptr;
     if (saved) saved_floats(*net, n, saved, us.data(), &stem_z);
@@ -474,6 +466,8 @@ SMC_API int smc_irse_forward_f32(const smc_irse_net* net, const float* img, int 
         }
         // g = sigmoid(W2 relu(W1 m)); out = r * g + shortcut (+ BN1 of the next unit): one fused launch
         float* out = x == w.xa ? w.xb : w.xa;
+        for (int t = 0; t < ntaps; ++t)
+            if (tap_units[t] == k) out = tap_out[t];  // a tapped unit writes its output into the caller's buffer
         const bool next = k + 1 < net->n_units;
         hipLaunchKernelGGL(se_fwd_combine_kernel, dim3(n, u.depth / kSeCpb, se_zsplit(ohw)), dim3(256),
                            sizeof(float) * (u.depth + u.se_hidden + 3 * kSeCpb), st, w.m, u.se_w1, u.se_w2, hbuf, gbuf,
@@ -482,11 +476,61 @@ SMC_API int smc_irse_forward_f32(const smc_irse_net* net, const float* img, int 
         SMC_TRY(smc::check_launch("irse se + combine"));
         x = out;
     }
+    *x_out = x;
+    return SMC_OK;
+}
+
+}  // namespace
+
+SMC_API int64_t smc_irse_saved_floats(const smc_irse_net* net, int n) {
+    if (net_validate(net, n) != SMC_OK) return -1;
+    return saved_floats(*net, n, nullptr, nullptr, nullptr);
+}
+
+SMC_API int64_t smc_irse_workspace_bytes(const smc_irse_net* net, int n) {
+    if (net_validate(net, n) != SMC_OK) return -1;
+    return ws_floats(*net, n, nullptr, nullptr) * (int64_t)sizeof(float);
+}
+
+SMC_API int smc_irse_forward_f32(const smc_irse_net* net, const float* img, int n, float* feat, float* saved,
+                                 float* workspace, int64_t workspace_bytes, void* stream) {
+    SMC_TRY(net_validate(net, n));
+    SMC_CHECK(img && feat && workspace, "smc_irse_forward_f32: null pointer");
+    SMC_CHECK(workspace_bytes >= ws_floats(*net, n, nullptr, nullptr) * (int64_t)sizeof(float),
+              "smc_irse_forward_f32: workspace too small");
+    Ws w;
+    ws_floats(*net, n, workspace, &w);
+    float* x = nullptr;
+    SMC_TRY(forward_body(net, img, n, saved, w, stream, nullptr, nullptr, 0, &x));
     // output layer: folded BN2d + Linear + BN1d
     smc_linear_epilogue le{};
     le.bias = net->fc_b;
     return smc_linear_f32(x, net->flat, net->fc_wt, net->feat, feat, net->feat, n, net->feat, net->flat, &le, w.conv,
                           w.conv_bytes, stream);
+}
+
+SMC_API int64_t smc_irse_trunk_workspace_bytes(const smc_irse_net* net, int n) {
+    if (trunk_validate(net, n) != SMC_OK) return -1;
+    return ws_floats(*net, n, nullptr, nullptr) * (int64_t)sizeof(float);
+}
+
+SMC_API int smc_irse_trunk_f32(const smc_irse_net* net, const float* img, int n, const int* tap_units,
+                               float* const* tap_out, int ntaps, float* workspace, int64_t workspace_bytes,
+                               void* stream) {
+    SMC_TRY(trunk_validate(net, n));
+    SMC_CHECK(img && workspace && tap_units && tap_out, "smc_irse_trunk_f32: null pointer");
+    SMC_CHECK(ntaps >= 1 && ntaps <= 3, "smc_irse_trunk_f32: %d taps (1..3)", ntaps);
+    for (int t = 0; t < ntaps; ++t) {
+        SMC_CHECK(tap_units[t] >= 0 && tap_units[t] < net->n_units && tap_out[t],
+                  "smc_irse_trunk_f32: tap %d names unit %d of %d", t, tap_units[t], net->n_units);
+        SMC_CHECK(t == 0 || tap_units[t] > tap_units[t - 1], "smc_irse_trunk_f32: tap units must ascend");
+    }
+    SMC_CHECK(workspace_bytes >= ws_floats(*net, n, nullptr, nullptr) * (int64_t)sizeof(float),
+              "smc_irse_trunk_f32: workspace too small");
+    Ws w;
+    ws_floats(*net, n, workspace, &w);
+    float* x = nullptr;
+    return forward_body(net, img, n, nullptr, w, stream, tap_units, tap_out, ntaps, &x);
 }
 
 SMC_API int smc_irse_backward_f32(const smc_irse_net* net, const float* dfeat, int n_saved, int n, const float* saved,

@@ -83,7 +83,9 @@ X3 = False
 class _Packed:
     """Device tensors + ctypes descriptors of one IR-SE50 (kept alive together)."""
 
-    def __init__(self, net: Backbone, device, in_hw=112):
+    def __init__(self, net: Backbone, device, in_hw=112, output_layer=True):
+        """output_layer=False: stem and units only (feat = flat = 0, no fc_*), for smc_irse_trunk_f32 -- ``net`` then
+        needs ``input_layer`` and ``body`` alone (the e4e / pSp encoders)."""
         self.keep = []
         dev = torch.device(device)
 
@@ -207,19 +209,20 @@ class _Packed:
         nt.n_units = len(units)
         nt.units = ctypes.cast(self.units, P)
 
-        # ---- output layer: BatchNorm2d -> Dropout (eval: identity) -> flatten -> Linear -> BatchNorm1d
-        bno, fc, bnf = net.output_layer[0], net.output_layer[3], net.output_layer[4]
-        ao, bo = bn_affine(bno)
-        af, bf = bn_affine(bnf)
-        Wl = fc.weight.detach().double().cpu()                     # [feat][flat], flat index = c*hw*hw + p
-        feat, flat = Wl.shape
-        rep = flat // ao.numel()
-        Wf = Wl * ao.repeat_interleave(rep)[None, :]
-        fb = fc.bias.detach().double().cpu() + Wl @ bo.repeat_interleave(rep)
-        Wf = Wf * af[:, None]
-        fb = fb * af + bf
-        nt.feat, nt.flat = feat, flat
-        nt.fc_wt, nt.fc_w, nt.fc_b = ptr(Wf.t()), ptr(Wf), ptr(fb)
+        if output_layer:
+            # ---- output layer: BatchNorm2d -> Dropout (eval: identity) -> flatten -> Linear -> BatchNorm1d
+            bno, fc, bnf = net.output_layer[0], net.output_layer[3], net.output_layer[4]
+            ao, bo = bn_affine(bno)
+            af, bf = bn_affine(bnf)
+            Wl = fc.weight.detach().double().cpu()                     # [feat][flat], flat index = c*hw*hw + p
+            feat, flat = Wl.shape
+            rep = flat // ao.numel()
+            Wf = Wl * ao.repeat_interleave(rep)[None, :]
+            fb = fc.bias.detach().double().cpu() + Wl @ bo.repeat_interleave(rep)
+            Wf = Wf * af[:, None]
+            fb = fb * af + bf
+            nt.feat, nt.flat = feat, flat
+            nt.fc_wt, nt.fc_w, nt.fc_b = ptr(Wf.t()), ptr(Wf), ptr(fb)
         if dev.type == "cuda":  # the packed weights (and Winograd taps) are complete before any stream reads them
             torch.cuda.current_stream(dev).synchronize()
 

@@ -143,6 +143,20 @@ def seeded_state_dict(module, seed=0):
     return out
 
 
+def e4e_state_dict(module, seed=0):
+    """seeded_state_dict for the e4e / pSp encoders with the heads' conv weights (``styles.*.convs.*.weight``) and the
+    lateral convs (``latlayer*.weight``) doubled.  With the plain 1/fan_in weights the heads' outputs are dominated by
+    their biases (at 64 px the input-dependent part of a W+ row has std 0.8-1.2e-3 of a row std of 0.027, so a wrong
+    conv would hide under any sensible tolerance); doubled it is 0.013-0.049 of 0.072 at 64 px and 0.15-0.48 of 0.64 at
+    256 px (CPU measurements on the reference module)."""
+    out = seeded_state_dict(module, seed=seed)
+    for key in out:
+        parts = key.split(".")
+        if parts[-1] == "weight" and ((parts[0] == "styles" and "convs" in parts) or parts[0].startswith("latlayer")):
+            out[key] = out[key] * 2
+    return out
+
+
 def _is_prelu(module, key):
     mod = module
     for part in key.split(".")[:-1]:
