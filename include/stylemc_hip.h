@@ -290,9 +290,10 @@ int smc_modconv_epilogue_f32(const float* src, int nsplit, int64_t split_stride,
  * then the modconv epilogue (u_save receives U).  T: [n, c, t_h, t_pitch] of which the first t_w columns
  * are the image (t_pitch = 0: t_w; a pitch that is a multiple of 4 -- the transposed conv's odd 2h + 1
  * width padded -- takes the 16-B load path), may be `nsplit` partial planes; y: [n, c, y_h, y_w].  Only
- * the 4x4 FIR of the [1,3,3,1] resample filter has a fused kernel; other sizes return SMC_ERR_UNSUPPORTED.
- * f = NULL (fh = fw = 4): the built-in setup_filter([1,3,3,1]) taps as compile-time constants (bit-identical to
- * passing that filter; the kernel then holds no taps in registers). */
+ * 4x4 filters have the fast kernels; any other size up to 8x8 runs a generic tile kernel, larger ones return
+ * SMC_ERR_UNSUPPORTED.  f = NULL (fh = fw = 4): the built-in setup_filter([1,3,3,1]) taps as compile-time constants
+ * (bit-identical to passing that filter; the kernel then holds no taps in registers).  epi must not be NULL (pass
+ * mode SMC_EPI_STORE for the bare FIR): SMC_ERR_INVALID otherwise. */
 int smc_modconv_blur_act_f32(const float* t, int nsplit, int64_t split_stride, float* y, int n, int c, int t_h,
                              int t_w, int t_pitch, int y_h, int y_w, const float* f, int fh, int fw, int padx0,
                              int pady0, float fgain, int flip, const smc_conv_epilogue* epi, void* stream);
@@ -323,7 +324,9 @@ const char* smc_modconv_up2_route_name(int route);
 /* Backward of smc_modconv_blur_act_f32 in one pass: du = bias_act'(g; y re-derived from u) * d[n,o],
  * dt = adjoint FIR of du (pad (pady0, padx0) = (fh-1-p, fw-1-p) of the forward pad p, flip, gain fgain;
  * upfirdn2d.py:245-264 rule), and if dd != NULL: dd[n,o] += sum_hw dz*u.  g/u: [n,c,u_h,u_w],
- * dt: [n,c,t_h,t_pitch] (t_pitch = 0: t_w; columns >= t_w are not written).  4x4 filters only
+ * dt: [n,c,t_h,t_pitch] (t_pitch = 0: t_w; columns >= t_w are not written).  dt: any adjoint pad >= 0 (a
+ * negative one is SMC_ERR_INVALID).  dd: adjoint pads 0 .. 3 in both axes (below 2, t is smaller than u: dd still sums
+ * the whole u plane); dd != NULL with a pad above 3 is SMC_ERR_UNSUPPORTED.  4x4 filters only
  * (SMC_ERR_UNSUPPORTED otherwise); f = NULL: the built-in [1,3,3,1] taps (as smc_modconv_blur_act_f32). */
 int smc_modconv_blur_act_bwd_f32(const float* g, const float* u, float* dt, float* dd, int n, int c, int u_h, int u_w,
                                  int t_h, int t_w, int t_pitch, const float* f, int fh, int fw, int padx0, int pady0,
@@ -385,6 +388,22 @@ int smc_torgb_bwd_f32(const float* g, const float* y, const float* w, const floa
 int smc_torgb_act_bwd_f32(const float* g_rgb, const float* y_rgb, const float* w, const float* s, float clamp_rgb,
                           const float* g_next, const float* y, float* du, int n, int cin, int cout, int h, int w_,
                           const smc_conv_epilogue* epi, void* stream);
+
+/* Launch report of the memory-bound companion kernels: this thread's last call to smc_modconv_epilogue_f32,
+ * smc_modconv_blur_act_f32 / _bwd_f32, smc_modconv_demod_f32 / _bwd_f32, smc_modconv_act_bwd_f32, smc_channel_dot_f32
+ * or smc_torgb_fwd_f32 / _bwd_f32 / _act_bwd_f32 (tests, attribution; no launch decision reads it; a dispatcher that
+ * calls one of them -- the Winograd split-K reduction -- records here too).  As smc_conv3x3_wino_last_route: 0
+ * ("none") when the call failed before its launch, else the kernel instantiation, numbered 1 ..
+ * smc_modconv_aux_route_count() - 1 and named as written in its launch (smc_modconv_aux_route_name; NULL outside the
+ * range; compare names, never numbers, across builds).  Flags: SMC_ROUTE_DD_PARTIALS when the two-level dd sum ran
+ * (per-tile partials in the workspace, then dd_sum_kernel).  smc_modconv_aux_last_nsplit: the grid.z channel split of
+ * smc_torgb_act_bwd_f32, 1 for every other entry point. */
+#define SMC_ROUTE_DD_PARTIALS 32
+int smc_modconv_aux_last_route(void);
+int smc_modconv_aux_last_route_flags(void);
+int smc_modconv_aux_last_nsplit(void);
+int smc_modconv_aux_route_count(void);
+const char* smc_modconv_aux_route_name(int route);
 
 /* IDLoss face crop (id_loss.py:20-23): y[p] = adaptive_avg_pool(crop(adaptive_avg_pool(x[p], (pool_h, pool_w)),
  * [crop_y0 : crop_y0+crop_h, crop_x0 : crop_x0+crop_w]), (out_h, out_w)) for `planes` planes; the first pool

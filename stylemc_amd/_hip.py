@@ -21,6 +21,7 @@ ACT_CODES = {"linear": 1, "relu": 2, "lrelu": 3, "tanh": 4, "sigmoid": 5, "elu":
 EPI_STORE, EPI_MODACT, EPI_PRELU, EPI_PRELU_GRAD, EPI_AFFINE = 0, 1, 2, 3, 4
 ROUTE_SPLIT_K, ROUTE_PER_SAMPLE, ROUTE_PRESCALE, ROUTE_WSAMPLE = 1, 2, 4, 8
 ROUTE_WINO_FOLD = 16
+ROUTE_DD_PARTIALS = 32
 
 
 class ConvPhase(ctypes.Structure):
@@ -118,6 +119,11 @@ _SIGS = {
     "smc_torgb_fwd_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     "smc_torgb_bwd_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P]),
     "smc_torgb_act_bwd_f32": (c_int, [P, P, P, P, c_float, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "smc_modconv_aux_last_route": (c_int, []),
+    "smc_modconv_aux_last_route_flags": (c_int, []),
+    "smc_modconv_aux_last_nsplit": (c_int, []),
+    "smc_modconv_aux_route_count": (c_int, []),
+    "smc_modconv_aux_route_name": (c_char_p, [c_int]),
     "smc_face_crop_f32": (c_int, [P, c_int64] + [c_int] * 10 + [P, P]),
     "smc_face_crop_bwd_f32": (c_int, [P, c_int64] + [c_int] * 10 + [P, P]),
     "smc_clip_unprocess_f32": (c_int, [P] + [c_int] * 6 + [P, P, P, P]),

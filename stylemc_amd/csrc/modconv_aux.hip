@@ -8,6 +8,7 @@
 //   * gradient through the demodulation               (smc_modconv_demod_bwd_f32)
 // The forward replaces the bias_act / upfirdn2d / fma launches the reference issues after each
 // grouped conv ([upstream] SynthesisLayer.forward -> bias_act.py:153, upfirdn2d.py:237, fma.py:15).
+#include "aux_routes.hpp"
 #include "common.hpp"
 #include "fir_epi.hpp"
 
@@ -372,6 +373,8 @@ __global__ __launch_bounds__(256) void blur_act_fast(const float* t, int nsplit,
 // before the next layer's conv has streamed the whole plane set).  Measured (profiles/r04/blur_ab/, bit-identical y):
 // TPB 4 + NT 712 -> 650 us over the five conv0 layers; TPB 8 / 16 no better; the same on the backward lost (dT is read
 // right away by the transposed conv's data gradient).
+constexpr int kBlurTPB = SMC_BLUR_TPB;
+constexpr bool kBlurNT = SMC_BLUR_NT != 0;
 template <int FH, int FW, int TPB, bool NT, bool STDF = false>
 __global__ __launch_bounds__(256, STDF ? SMC_BLUR_WGS : 1) void blur_act_v4(const float* t, int nsplit, int64_t split_stride, float* y, int c,
                                                    int t_h, int t_w, int tp_w, int y_h, int y_w, const float* f,
@@ -484,7 +487,9 @@ __global__ __launch_bounds__(256, STDF ? SMC_BLUR_WGS : 1) void blur_act_v4(cons
 
 // Backward of conv0's epilogue + FIR in one pass: du = act'(g; y(u)) * d (re-derived per element of the
 // haloed tile), dT = FIR^T(du) (pad (pady0, padx0) of the adjoint), dd[n,o] += sum dz*u over the du
-// positions this tile owns (its own 32x64 window, so every position is counted exactly once).
+// positions this tile owns (its own 32x64 window, the grid's last row / column of tiles also what lies beyond it, so
+// every position is counted exactly once at an adjoint pad 0 .. 3; beyond 3 a tile's haloed window no longer holds the
+// last rows / columns of its own 32x64, and the host rejects dd).
 // FROMY (epi.grad_from_y): `u` holds the forward output y -- the mask needs nothing else; no noise read, no dd.
 template <int FH, int FW, bool V2 = false, bool FROMY = false>
 __global__ __launch_bounds__(256) void blur_act_bwd_fast(const float* g, const float* u, float* dt, float* dd, int c,
@@ -496,6 +501,11 @@ __global__ __launch_bounds__(256) void blur_act_bwd_fast(const float* g, const f
     __shared__ float red[4];
     const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
     const int ox0 = blockIdx.y * kFW, oy0 = blockIdx.z * kFH;  // fir_grid_bwd
+    // the last tile of a row / column of the t grid also owns the u columns / rows beyond its window's 64 / 32 (an
+    // adjoint pad below 2 makes t smaller than u; its haloed window reaches u's last row and column at every pad >= 0).
+    // Every owned position is inside the window (rows oy0 - pady0 .. + 34, columns likewise) only while the pad is <= 3:
+    // the host passes no dd beyond that.
+    const int ox1 = blockIdx.y == gridDim.y - 1 ? u_w : ox0 + kFW, oy1 = blockIdx.z == gridDim.z - 1 ? u_h : oy0 + kFH;
     const int64_t nc = blockIdx.x;
     const int n = (int)(nc / c), o = (int)(nc - (int64_t)n * c);
     float tp[FH][FW];
@@ -514,7 +524,7 @@ __global__ __launch_bounds__(256) void blur_act_bwd_fast(const float* g, const f
         if constexpr (FROMY) return smc::act_grad_y(e.act, gg, uu, e.alpha, e.gain, e.clamp) * dv;
         const float yv = smc::epi_y(uu, dv, nn * nstr, bv, e.act, e.alpha, e.gain, e.clamp);
         const float dz = smc::act_grad_y(e.act, gg, yv, e.alpha, e.gain, e.clamp);
-        if (iy >= oy0 && iy < oy0 + kFH && ix >= ox0 && ix < ox0 + kFW) part += dz * uu;
+        if (iy >= oy0 && iy < oy1 && ix >= ox0 && ix < ox1) part += dz * uu;
         return dz * dv;
     };
     if constexpr (V2) {
@@ -606,6 +616,11 @@ __global__ __launch_bounds__(256) void blur_act_bwd_v4(const float* g, const flo
     __shared__ float red[4];
     const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
     const int ox0 = blockIdx.y * kFW, oy0 = blockIdx.z * kFH;  // fir_grid_bwd
+    // the last tile of a row / column of the t grid also owns the u columns / rows beyond its window's 64 / 32 (an
+    // adjoint pad below 2 makes t smaller than u; its haloed window reaches u's last row and column at every pad >= 0).
+    // Every owned position is inside the window (rows oy0 - pady0 .. + 34, columns likewise) only while the pad is <= 3:
+    // the host passes no dd beyond that.
+    const int ox1 = blockIdx.y == gridDim.y - 1 ? u_w : ox0 + kFW, oy1 = blockIdx.z == gridDim.z - 1 ? u_h : oy0 + kFH;
     const int64_t nc = blockIdx.x;
     const int n = (int)(nc / c), o = (int)(nc - (int64_t)n * c);
     float tp[FH][FW];
@@ -654,7 +669,7 @@ __global__ __launch_bounds__(256) void blur_act_bwd_v4(const float* g, const flo
                 } else {
                     const float yv = smc::epi_y(ua[k], dv, na[k] * nstr, bv, e.act, e.alpha, e.gain, e.clamp);
                     const float dz = smc::act_grad_y(e.act, ga[k], yv, e.alpha, e.gain, e.clamp);
-                    if (iy >= oy0 && iy < oy0 + kFH && ix >= ox0 && ix < ox0 + kFW) part += dz * ua[k];
+                    if (iy >= oy0 && iy < oy1 && ix >= ox0 && ix < ox1) part += dz * ua[k];
                     val = dz * dv;
                 }
             }
@@ -901,14 +916,46 @@ int64_t grid_cap(int64_t blocks) {
     return blocks < 1 ? 1 : blocks;
 }
 
+// Launch report (smc_modconv_aux_last_route; aux_routes.hpp): the names are the launches' own kernel tokens.
+#define SMC_AUX_STR2(...) #__VA_ARGS__
+#define SMC_AUX_STR(...) SMC_AUX_STR2(__VA_ARGS__)
+#define SMC_AUX_NAME(id) SMC_AUX_STR(SMC_AUXK_##id),
+constexpr const char* kAuxRouteNames[] = {"none", SMC_AUX_ROUTES(SMC_AUX_NAME)};
+#undef SMC_AUX_NAME
+static_assert(sizeof(kAuxRouteNames) / sizeof(kAuxRouteNames[0]) == smc::AUX_COUNT, "one name per route");
+
+thread_local int g_aux_route = smc::AUX_NONE;
+thread_local int g_aux_flags = 0;    // SMC_ROUTE_DD_PARTIALS of that call
+thread_local int g_aux_nsplit = 1;   // grid.z of smc_torgb_act_bwd_f32 (1 for everything else)
+
 }  // namespace
+
+namespace smc {
+void aux_route_begin() { g_aux_route = AUX_NONE; g_aux_flags = 0; g_aux_nsplit = 1; }
+void aux_route_set(int route) { g_aux_route = route; }
+void aux_route_flag(int flag) { g_aux_flags |= flag; }
+void aux_route_nsplit(int nsplit) { g_aux_nsplit = nsplit; }
+}  // namespace smc
+
+SMC_API int smc_modconv_aux_last_route(void) { return g_aux_route; }
+
+SMC_API int smc_modconv_aux_last_route_flags(void) { return g_aux_flags; }
+
+SMC_API int smc_modconv_aux_last_nsplit(void) { return g_aux_nsplit; }
+
+SMC_API int smc_modconv_aux_route_count(void) { return smc::AUX_COUNT; }
+
+SMC_API const char* smc_modconv_aux_route_name(int route) {
+    return route >= 0 && route < smc::AUX_COUNT ? kAuxRouteNames[route] : nullptr;
+}
 
 SMC_API int smc_modconv_epilogue_f32(const float* src, int nsplit, int64_t split_stride, float* y, int n, int c, int h,
                                      int w, const smc_conv_epilogue* epi, void* stream) {
+    smc::aux_route_begin();
     SMC_CHECK(src && y && n >= 1 && c >= 1 && h >= 1 && w >= 1 && nsplit >= 1, "smc_modconv_epilogue_f32: bad args");
     const int64_t total = (int64_t)n * c * h * w;
-    hipLaunchKernelGGL(epilogue_kernel, dim3((unsigned)grid_cap(smc::ceil_div(total, 256))), dim3(256), 0,
-                       smc::as_stream(stream), src, nsplit, split_stride, y, c, h, w, total, to_epi(epi));
+    SMC_AUX_LAUNCH(EPILOGUE, dim3((unsigned)grid_cap(smc::ceil_div(total, 256))), smc::as_stream(stream), src, nsplit,
+                   split_stride, y, c, h, w, total, to_epi(epi));
     return smc::check_launch("smc_modconv_epilogue_f32");
 }
 
@@ -916,8 +963,10 @@ SMC_API int smc_modconv_blur_act_f32(const float* t, int nsplit, int64_t split_s
                                      int t_h, int t_w, int t_pitch, int y_h, int y_w, const float* f, int fh, int fw,
                                      int padx0, int pady0, float fgain, int flip, const smc_conv_epilogue* epi,
                                      void* stream) {
+    smc::aux_route_begin();
     SMC_CHECK(t && y && (f || (fh == 4 && fw == 4)) && n >= 1 && c >= 1 && nsplit >= 1,
               "smc_modconv_blur_act_f32: bad args");
+    SMC_CHECK(epi, "smc_modconv_blur_act_f32: needs an epilogue (SMC_EPI_STORE for the bare FIR)");
     if (fh > kMaxF || fw > kMaxF || fh < 1 || fw < 1) {
         smc::set_error("smc_modconv_blur_act_f32: filter %dx%d > %dx%d", fh, fw, kMaxF, kMaxF);
         return SMC_ERR_UNSUPPORTED;
@@ -936,29 +985,29 @@ SMC_API int smc_modconv_blur_act_f32(const float* t, int nsplit, int64_t split_s
         if (v4) {
             grid.y = (unsigned)smc::ceil_div((int)grid.y, SMC_BLUR_TPB);
             if (SMC_BLUR_STDF && !f && fgain == 4.f)   // the built-in resample filter with the conv0 gain: compile-time taps
-                hipLaunchKernelGGL((blur_act_v4<4, 4, SMC_BLUR_TPB, SMC_BLUR_NT != 0, true>), grid, dim3(256), 0, st, t, nsplit,
-                                   split_stride, y, c, t_h, t_w, tp_w, y_h, y_w, f, padx0, pady0, fgain, flip, to_epi(epi));
+                SMC_AUX_LAUNCH(BLUR_V4_STD, grid, st, t, nsplit, split_stride, y, c, t_h, t_w, tp_w, y_h, y_w, f, padx0,
+                               pady0, fgain, flip, to_epi(epi));
             else
-                hipLaunchKernelGGL((blur_act_v4<4, 4, SMC_BLUR_TPB, SMC_BLUR_NT != 0>), grid, dim3(256), 0, st, t, nsplit,
-                                   split_stride, y, c, t_h, t_w, tp_w, y_h, y_w, f, padx0, pady0, fgain, flip, to_epi(epi));
+                SMC_AUX_LAUNCH(BLUR_V4, grid, st, t, nsplit, split_stride, y, c, t_h, t_w, tp_w, y_h, y_w, f, padx0,
+                               pady0, fgain, flip, to_epi(epi));
         } else {
-            hipLaunchKernelGGL((blur_act_fast<4, 4>), grid, dim3(256), 0, st, t, nsplit, split_stride, y, c, t_h, t_w,
-                               tp_w, y_h, y_w, f, padx0, pady0, fgain, flip, to_epi(epi));
+            SMC_AUX_LAUNCH(BLUR_FAST, grid, st, t, nsplit, split_stride, y, c, t_h, t_w, tp_w, y_h, y_w, f, padx0, pady0,
+                           fgain, flip, to_epi(epi));
         }
         return smc::check_launch("smc_modconv_blur_act_f32");
     }
     dim3 grid((unsigned)smc::ceil_div(y_w, kBT), (unsigned)smc::ceil_div(y_h, kBT), (unsigned)(n * c));
-    hipLaunchKernelGGL(blur_act_kernel, grid, dim3(256), 0, st, t, nsplit, split_stride, y, c, t_h, t_w, tp_w, y_h, y_w,
-                       f, fh, fw, padx0, pady0, fgain, flip, to_epi(epi));
+    SMC_AUX_LAUNCH(BLUR_GENERIC, grid, st, t, nsplit, split_stride, y, c, t_h, t_w, tp_w, y_h, y_w, f, fh, fw, padx0,
+                   pady0, fgain, flip, to_epi(epi));
     return smc::check_launch("smc_modconv_blur_act_f32");
 }
 
 SMC_API int smc_modconv_demod_f32(const float* s, const float* wsq, float* d, int n, int cin, int cout, float eps,
                                   void* stream) {
+    smc::aux_route_begin();
     SMC_CHECK(s && wsq && d && n >= 1 && cin >= 1 && cout >= 1, "smc_modconv_demod_f32: bad args");
     const int64_t rows = (int64_t)n * cout;
-    hipLaunchKernelGGL(demod_kernel, dim3((unsigned)smc::ceil_div(rows, 4)), dim3(256), 0, smc::as_stream(stream), s,
-                       wsq, d, n, cin, cout, eps);
+    SMC_AUX_LAUNCH(DEMOD, dim3((unsigned)smc::ceil_div(rows, 4)), smc::as_stream(stream), s, wsq, d, n, cin, cout, eps);
     return smc::check_launch("smc_modconv_demod_f32");
 }
 
@@ -978,6 +1027,7 @@ SMC_API int64_t smc_modconv_act_bwd_workspace_size(int n, int c, int h, int w) {
 SMC_API int smc_modconv_act_bwd_f32(const float* g, const float* u, float* du, float* dd, int n, int c, int h, int w,
                                     const smc_conv_epilogue* epi, void* workspace, int64_t workspace_bytes,
                                     void* stream) {
+    smc::aux_route_begin();
     SMC_CHECK(g && u && du && n >= 1 && c >= 1 && h >= 1 && w >= 1, "smc_modconv_act_bwd_f32: bad args");
     SMC_CHECK(epi && epi->mode == SMC_EPI_MODACT, "smc_modconv_act_bwd_f32: needs a MODACT epilogue");
     const bool from_y = epi->grad_from_y != 0;
@@ -1000,17 +1050,17 @@ SMC_API int smc_modconv_act_bwd_f32(const float* g, const float* u, float* du, f
         e.dd_part = static_cast<float*>(workspace);
         ddk = nullptr;
     }
+    const dim3 grid((unsigned)blocks_per_plane, (unsigned)planes);
     if (vec4) {
-        const dim3 grid((unsigned)blocks_per_plane, (unsigned)planes);
-        if (from_y) hipLaunchKernelGGL(act_bwd_vec4_kernel<true>, grid, dim3(256), 0, st, g, u, du, ddk, c, hw, e);
-        else hipLaunchKernelGGL(act_bwd_vec4_kernel<false>, grid, dim3(256), 0, st, g, u, du, ddk, c, hw, e);
+        if (from_y) SMC_AUX_LAUNCH(ACT_BWD_V4_Y, grid, st, g, u, du, ddk, c, hw, e);
+        else SMC_AUX_LAUNCH(ACT_BWD_V4_U, grid, st, g, u, du, ddk, c, hw, e);
     } else {
-        const dim3 grid((unsigned)blocks_per_plane, (unsigned)planes);
-        if (from_y) hipLaunchKernelGGL(act_bwd_kernel<true>, grid, dim3(256), 0, st, g, u, du, ddk, c, hw, e);
-        else hipLaunchKernelGGL(act_bwd_kernel<false>, grid, dim3(256), 0, st, g, u, du, ddk, c, hw, e);
+        if (from_y) SMC_AUX_LAUNCH(ACT_BWD_Y, grid, st, g, u, du, ddk, c, hw, e);
+        else SMC_AUX_LAUNCH(ACT_BWD_U, grid, st, g, u, du, ddk, c, hw, e);
     }
     int rc = smc::check_launch("smc_modconv_act_bwd_f32");
     if (two_level && rc == SMC_OK) {
+        smc::aux_route_flag(SMC_ROUTE_DD_PARTIALS);
         hipLaunchKernelGGL(dd_sum_kernel, dim3((unsigned)smc::ceil_div(planes, 4)), dim3(256), 0, st, e.dd_part,
                            blocks_per_plane, dd, planes);
         rc = smc::check_launch("smc_modconv_act_bwd_f32 (dd)");
@@ -1020,26 +1070,28 @@ SMC_API int smc_modconv_act_bwd_f32(const float* g, const float* u, float* du, f
 
 SMC_API int smc_channel_dot_f32(const float* a, const float* b, const float* scale, float* out, float* a_scaled,
                                 int64_t rows, int64_t len, int accumulate, void* stream) {
+    smc::aux_route_begin();
     SMC_CHECK(a && b && out && rows >= 1 && len >= 1, "smc_channel_dot_f32: bad args");
     SMC_CHECK(!a_scaled || scale, "smc_channel_dot_f32: a_scaled needs scale");
     SMC_CHECK(rows < (1LL << 31), "smc_channel_dot_f32: too many rows");
     if (len % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)a_scaled) & 15) == 0) {
-        hipLaunchKernelGGL(channel_dot_v4_kernel, dim3((unsigned)rows), dim3(256), 0, smc::as_stream(stream),
-                           reinterpret_cast<const float4*>(a), reinterpret_cast<const float4*>(b), scale, out,
-                           reinterpret_cast<float4*>(a_scaled), len / 4, accumulate);
+        SMC_AUX_LAUNCH(CHANNEL_DOT_V4, dim3((unsigned)rows), smc::as_stream(stream), reinterpret_cast<const float4*>(a),
+                       reinterpret_cast<const float4*>(b), scale, out, reinterpret_cast<float4*>(a_scaled), len / 4,
+                       accumulate);
         return smc::check_launch("smc_channel_dot_f32");
     }
-    hipLaunchKernelGGL(channel_dot_kernel, dim3((unsigned)rows), dim3(256), 0, smc::as_stream(stream), a, b, scale,
-                       out, a_scaled, len, accumulate);
+    SMC_AUX_LAUNCH(CHANNEL_DOT, dim3((unsigned)rows), smc::as_stream(stream), a, b, scale, out, a_scaled, len,
+                   accumulate);
     return smc::check_launch("smc_channel_dot_f32");
 }
 
 SMC_API int smc_modconv_demod_bwd_f32(const float* s, const float* d, const float* dd, const float* wsq, float* ds,
                                       int n, int cin, int cout, void* stream) {
+    smc::aux_route_begin();
     SMC_CHECK(s && d && dd && wsq && ds && n >= 1 && cin >= 1 && cout >= 1, "smc_modconv_demod_bwd_f32: bad args");
     SMC_CHECK(n < 65536, "smc_modconv_demod_bwd_f32: batch too large");
-    hipLaunchKernelGGL(demod_bwd_kernel, dim3((unsigned)smc::ceil_div(cin, 32), (unsigned)n), dim3(256), 0,
-                       smc::as_stream(stream), s, d, dd, wsq, ds, cin, cout);
+    SMC_AUX_LAUNCH(DEMOD_BWD, dim3((unsigned)smc::ceil_div(cin, 32), (unsigned)n), smc::as_stream(stream), s, d, dd, wsq,
+                   ds, cin, cout);
     return smc::check_launch("smc_modconv_demod_bwd_f32");
 }
 
@@ -1060,10 +1112,12 @@ SMC_API int smc_modconv_blur_act_bwd_f32(const float* g, const float* u, float* 
                                          int u_w, int t_h, int t_w, int t_pitch, const float* f, int fh, int fw,
                                          int padx0, int pady0, float fgain, int flip, const smc_conv_epilogue* epi,
                                          void* workspace, int64_t workspace_bytes, void* stream) {
+    smc::aux_route_begin();
     SMC_CHECK(g && u && dt && (f || (fh == 4 && fw == 4)) && n >= 1 && c >= 1 && u_h >= 1 && u_w >= 1,
               "smc_modconv_blur_act_bwd_f32: bad args");
     SMC_CHECK(epi && epi->mode == SMC_EPI_MODACT, "smc_modconv_blur_act_bwd_f32: needs a MODACT epilogue");
-    SMC_CHECK(t_h == u_h + 2 * pady0 - fh + 1 && t_w == u_w + 2 * padx0 - fw + 1,
+    SMC_CHECK(padx0 >= 0 && pady0 >= 0, "smc_modconv_blur_act_bwd_f32: negative adjoint pad");
+    SMC_CHECK(t_h >= 1 && t_w >= 1 && t_h == u_h + 2 * pady0 - fh + 1 && t_w == u_w + 2 * padx0 - fw + 1,
               "smc_modconv_blur_act_bwd_f32: t shape does not match the adjoint FIR");
     const int tp_w = t_pitch > 0 ? t_pitch : t_w;
     SMC_CHECK(tp_w >= t_w, "smc_modconv_blur_act_bwd_f32: t_pitch < t_w");
@@ -1074,6 +1128,10 @@ SMC_API int smc_modconv_blur_act_bwd_f32(const float* g, const float* u, float* 
     }
     const bool from_y = epi->grad_from_y != 0;
     SMC_CHECK(!from_y || !dd, "smc_modconv_blur_act_bwd_f32: dd needs u (grad_from_y set)");
+    if (dd && (padx0 > 3 || pady0 > 3)) {   // a tile's haloed window would not hold all of the 32 x 64 it owns
+        smc::set_error("smc_modconv_blur_act_bwd_f32: dd needs an adjoint pad of at most 3 (got %d, %d)", padx0, pady0);
+        return SMC_ERR_UNSUPPORTED;
+    }
     hipStream_t st = smc::as_stream(stream);
     const dim3 grid = fir_grid_bwd((int64_t)n * c, t_w, t_h);
     Epi e = to_epi(epi);
@@ -1090,25 +1148,25 @@ SMC_API int smc_modconv_blur_act_bwd_f32(const float* g, const float* u, float* 
     }
     const uintptr_t al = (uintptr_t)g | (uintptr_t)u | (uintptr_t)(from_y ? nullptr : epi->noise);
     const int64_t nstr = from_y ? 0 : epi->noise_nstride;
-#define SMC_BLUR_BWD(KERNEL)                                                                                       \
-    hipLaunchKernelGGL(KERNEL, grid, dim3(256), 0, st, g, u, dt, dd, c, u_h, u_w, t_h, t_w, tp_w, f, padx0, pady0, \
-                       fgain, flip, e)
+#define SMC_BLUR_BWD(ID)                                                                                          \
+    SMC_AUX_LAUNCH(ID, grid, st, g, u, dt, dd, c, u_h, u_w, t_h, t_w, tp_w, f, padx0, pady0, fgain, flip, e)
     const bool stdf = SMC_BLUR_STDF && !f && fgain == 4.f;   // built-in [1,3,3,1] taps as constants
     if (u_w % 4 == 0 && nstr % 4 == 0 && (al & 15) == 0 && padx0 <= 4 && fw - 1 - padx0 <= 4) {
-        if (from_y && stdf) SMC_BLUR_BWD((blur_act_bwd_v4<4, 4, true, true>));
-        else if (from_y) SMC_BLUR_BWD((blur_act_bwd_v4<4, 4, true>));
-        else if (stdf) SMC_BLUR_BWD((blur_act_bwd_v4<4, 4, false, true>));
-        else SMC_BLUR_BWD((blur_act_bwd_v4<4, 4, false>));
+        if (from_y && stdf) SMC_BLUR_BWD(BLUR_BWD_V4_Y_STD);
+        else if (from_y) SMC_BLUR_BWD(BLUR_BWD_V4_Y);
+        else if (stdf) SMC_BLUR_BWD(BLUR_BWD_V4_U_STD);
+        else SMC_BLUR_BWD(BLUR_BWD_V4_U);
     } else if (u_w % 2 == 0 && padx0 % 2 == 0 && nstr % 2 == 0 && ((al & 7) == 0)) {
-        if (from_y) SMC_BLUR_BWD((blur_act_bwd_fast<4, 4, true, true>));
-        else SMC_BLUR_BWD((blur_act_bwd_fast<4, 4, true, false>));
+        if (from_y) SMC_BLUR_BWD(BLUR_BWD_V2_Y);
+        else SMC_BLUR_BWD(BLUR_BWD_V2_U);
     } else {
-        if (from_y) SMC_BLUR_BWD((blur_act_bwd_fast<4, 4, false, true>));
-        else SMC_BLUR_BWD((blur_act_bwd_fast<4, 4, false, false>));
+        if (from_y) SMC_BLUR_BWD(BLUR_BWD_S_Y);
+        else SMC_BLUR_BWD(BLUR_BWD_S_U);
     }
 #undef SMC_BLUR_BWD
     int rc = smc::check_launch("smc_modconv_blur_act_bwd_f32");
     if (two_level && rc == SMC_OK) {
+        smc::aux_route_flag(SMC_ROUTE_DD_PARTIALS);
         hipLaunchKernelGGL(dd_sum_kernel, dim3((unsigned)smc::ceil_div(planes, 4)), dim3(256), 0, st, e.dd_part,
                            tiles, dd_out, planes);
         rc = smc::check_launch("smc_modconv_blur_act_bwd_f32 (dd)");

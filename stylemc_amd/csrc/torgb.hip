@@ -4,6 +4,7 @@
 // grouped conv, conv2d_resample.py:29-54, then bias_act.py:153) called at utils.py:47.  With 3 output
 // channels this is an HBM-bound channel reduction, not a GEMM: each thread streams one float4 of
 // positions through all input channels, the [3 x cin] modulated weights of its sample sit in LDS.
+#include "aux_routes.hpp"
 #include "common.hpp"
 
 namespace {
@@ -317,6 +318,7 @@ __global__ __launch_bounds__(256) void torgb_bwd_small_kernel(const float* g, co
 
 SMC_API int smc_torgb_fwd_f32(const float* x, const float* w, const float* s, const float* b, float* y, int n, int cin,
                               int cout, int h, int w_, float clamp, void* stream) {
+    smc::aux_route_begin();
     SMC_CHECK(x && w && s && y && n >= 1 && cin >= 1 && h >= 1 && w_ >= 1, "smc_torgb_fwd_f32: bad args");
     SMC_CHECK(n < 65536, "smc_torgb_fwd_f32: batch too large");
     if (cout < 1 || cout > kMaxOut || cin > kMaxIn) {
@@ -325,22 +327,21 @@ SMC_API int smc_torgb_fwd_f32(const float* x, const float* w, const float* s, co
     }
     const int64_t hw = (int64_t)h * w_;
     if (hw <= kSmallHw) {
-        hipLaunchKernelGGL(torgb_fwd_small_kernel, dim3((unsigned)smc::ceil_div(hw, kFwdP), (unsigned)n), dim3(256), 0,
-                           smc::as_stream(stream), x, w, s, b, y, cin, cout, hw, clamp);
+        SMC_AUX_LAUNCH(TORGB_FWD_SMALL, dim3((unsigned)smc::ceil_div(hw, kFwdP), (unsigned)n), smc::as_stream(stream), x,
+                       w, s, b, y, cin, cout, hw, clamp);
         return smc::check_launch("smc_torgb_fwd_f32");
     }
     const bool vec = hw % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
     const int64_t per = vec ? hw / 4 : hw;
     dim3 grid((unsigned)smc::ceil_div(per, 256), (unsigned)n);
-    if (vec) hipLaunchKernelGGL(torgb_fwd_kernel<true>, grid, dim3(256), 0, smc::as_stream(stream), x, w, s, b, y, cin,
-                                cout, hw, clamp);
-    else hipLaunchKernelGGL(torgb_fwd_kernel<false>, grid, dim3(256), 0, smc::as_stream(stream), x, w, s, b, y, cin,
-                            cout, hw, clamp);
+    if (vec) SMC_AUX_LAUNCH(TORGB_FWD_VEC, grid, smc::as_stream(stream), x, w, s, b, y, cin, cout, hw, clamp);
+    else SMC_AUX_LAUNCH(TORGB_FWD, grid, smc::as_stream(stream), x, w, s, b, y, cin, cout, hw, clamp);
     return smc::check_launch("smc_torgb_fwd_f32");
 }
 
 SMC_API int smc_torgb_bwd_f32(const float* g, const float* y, const float* w, const float* s, float* dx, int n, int cin,
                               int cout, int h, int w_, float clamp, int scale, int accumulate, void* stream) {
+    smc::aux_route_begin();
     SMC_CHECK(g && y && w && dx && n >= 1 && cin >= 1 && h >= 1 && w_ >= 1, "smc_torgb_bwd_f32: bad args");
     SMC_CHECK(!scale || s, "smc_torgb_bwd_f32: scale needs s");
     SMC_CHECK(n < 65536, "smc_torgb_bwd_f32: batch too large");
@@ -351,23 +352,24 @@ SMC_API int smc_torgb_bwd_f32(const float* g, const float* y, const float* w, co
     const int64_t hw = (int64_t)h * w_;
     if (hw <= kSmallHw) {
         dim3 grid((unsigned)smc::ceil_div(hw, kBwdP), (unsigned)smc::ceil_div(cin, kBwdKCH), (unsigned)n);
-        hipLaunchKernelGGL(torgb_bwd_small_kernel, grid, dim3(256), 0, smc::as_stream(stream), g, y, w, s, dx, cin,
-                           cout, hw, clamp, scale, accumulate);
+        SMC_AUX_LAUNCH(TORGB_BWD_SMALL, grid, smc::as_stream(stream), g, y, w, s, dx, cin, cout, hw, clamp, scale,
+                       accumulate);
         return smc::check_launch("smc_torgb_bwd_f32");
     }
     const bool vec = hw % 4 == 0 && (reinterpret_cast<uintptr_t>(dx) & 15) == 0;
     const int64_t per = vec ? hw / 4 : hw;
     dim3 grid((unsigned)smc::ceil_div(per, 256), (unsigned)n);
-    if (vec) hipLaunchKernelGGL(torgb_bwd_kernel<true>, grid, dim3(256), 0, smc::as_stream(stream), g, y, w, s, dx, cin,
-                                cout, hw, clamp, scale, accumulate);
-    else hipLaunchKernelGGL(torgb_bwd_kernel<false>, grid, dim3(256), 0, smc::as_stream(stream), g, y, w, s, dx, cin,
-                            cout, hw, clamp, scale, accumulate);
+    if (vec) SMC_AUX_LAUNCH(TORGB_BWD_VEC, grid, smc::as_stream(stream), g, y, w, s, dx, cin, cout, hw, clamp, scale,
+                            accumulate);
+    else SMC_AUX_LAUNCH(TORGB_BWD, grid, smc::as_stream(stream), g, y, w, s, dx, cin, cout, hw, clamp, scale,
+                        accumulate);
     return smc::check_launch("smc_torgb_bwd_f32");
 }
 
 SMC_API int smc_torgb_act_bwd_f32(const float* g_rgb, const float* y_rgb, const float* w, const float* s,
                                   float clamp_rgb, const float* g_next, const float* y, float* du, int n, int cin,
                                   int cout, int h, int w_, const smc_conv_epilogue* epi, void* stream) {
+    smc::aux_route_begin();
     SMC_CHECK(g_rgb && y_rgb && w && s && y && du && n >= 1 && cin >= 1 && h >= 1 && w_ >= 1,
               "smc_torgb_act_bwd_f32: bad args");
     SMC_CHECK(epi && epi->mode == SMC_EPI_MODACT && epi->grad_from_y,
@@ -390,13 +392,12 @@ SMC_API int smc_torgb_act_bwd_f32(const float* g_rgb, const float* y_rgb, const 
     while (plan_wg * nz < 4 * (int64_t)smc::device_cu_count() && cin % (16 * nz) == 0) nz *= 2;
     grid.z = (unsigned)nz;
     const int kch = cin / nz;
+    smc::aux_route_nsplit(nz);
     if (vec)
-        hipLaunchKernelGGL(torgb_act_bwd_kernel<true>, grid, dim3(256), 0, smc::as_stream(stream), g_rgb, y_rgb, w, s,
-                           clamp_rgb, g_next, y, du, cin, cout, hw, epi->d, epi->act, epi->alpha, epi->gain, epi->clamp,
-                           kch);
+        SMC_AUX_LAUNCH(TORGB_ACT_BWD_VEC, grid, smc::as_stream(stream), g_rgb, y_rgb, w, s, clamp_rgb, g_next, y, du, cin,
+                       cout, hw, epi->d, epi->act, epi->alpha, epi->gain, epi->clamp, kch);
     else
-        hipLaunchKernelGGL(torgb_act_bwd_kernel<false>, grid, dim3(256), 0, smc::as_stream(stream), g_rgb, y_rgb, w, s,
-                           clamp_rgb, g_next, y, du, cin, cout, hw, epi->d, epi->act, epi->alpha, epi->gain, epi->clamp,
-                           kch);
+        SMC_AUX_LAUNCH(TORGB_ACT_BWD, grid, smc::as_stream(stream), g_rgb, y_rgb, w, s, clamp_rgb, g_next, y, du, cin,
+                       cout, hw, epi->d, epi->act, epi->alpha, epi->gain, epi->clamp, kch);
     return smc::check_launch("smc_torgb_act_bwd_f32");
 }

@@ -111,7 +111,7 @@ def test_route_tables_hold_only_tested_routes():
     GPU route tests is built to reach (EXPECTED) or one of the few those tests waive with a test of their own (the
     2 GiB inputs; the split-bf16 Winograd kernel that is off by default) -- so no instantiation that nothing can launch
     is compiled into the library, and no tested route has left it."""
-    from tests import conv_cases, wino_cases
+    from tests import aux_cases, conv_cases, wino_cases
     from tests.test_gpu_conv_routes import WAIVED as conv_waived
     from tests.test_gpu_wino_routes import WAIVED as wino_waived
     lib = _hip.load()
@@ -122,3 +122,6 @@ def test_route_tables_hold_only_tested_routes():
         expected = {wino_cases.EXPECTED[c.id][0] for c in wino_cases.CASES if c.fam == fam}
         expected |= {k for k in wino_waived if k.startswith("wino4_") == (fam == 4)}
         _check_route_names(count, name_of, expected)
+    # the companion kernels (modconv_aux.hip, torgb.hip): every route has a case, none is waived
+    _check_route_names(lib.smc_modconv_aux_route_count(), lib.smc_modconv_aux_route_name,
+                       {c.route for c in aux_cases.CASES})
