@@ -610,6 +610,27 @@ int smc_irse_forward_f32(const smc_irse_net* net, const float* img, int n, float
 int smc_irse_backward_f32(const smc_irse_net* net, const float* dfeat, int n_saved, int n, const float* saved,
                           float* dimg, float* workspace, int64_t workspace_bytes, void* stream);
 
+/* The squeeze-and-excite stage of one unit on its own: exactly the two launches each that smc_irse_forward_f32 /
+ * smc_irse_backward_f32 make per unit (the same host code), for tests at shapes the network never reaches.  Added
+ * under ABI version 6 without a version bump.  Limits, checked on the host before any launch (SMC_ERR_INVALID): n >= 1,
+ * C % 16 == 0, C <= 512, 1 <= hid <= 256, stride 1 or 2, in_h and in_w >= stride and divisible by it, n*C*oh*ow below
+ * 2^31, no NULL pointer but where one is allowed below.
+ *
+ * Forward, oh = in_h / stride, ow = in_w / stride:
+ *   m[n][C] = mean_hw r;  h[n][hid] = relu(w1 m);  g[n][C] = sigmoid(w2 h);  out = r * g[.., None, None] + shortcut;
+ *   xbn = out * a[c] + b[c]
+ *   r, out, xbn [n][C][oh][ow];  w1 [hid][C];  w2 [C][hid];  a, b [C].
+ *   shortcut: exactly one of sc [n][C][oh][ow] (the conv shortcut's output) and x [n][C][in_h][in_w] (the unit's input,
+ *   read at [stride*y][stride*x]: MaxPool2d(1, stride)) is non-NULL.  xbn, a and b are all NULL or all given. */
+int smc_irse_se_fwd_f32(const float* r, const float* sc, const float* x, int stride, int in_h, int in_w, int n, int C,
+                        const float* w1, const float* w2, int hid, const float* a, const float* b, float* out,
+                        float* xbn, float* h, float* g, float* m, void* stream);
+/* Backward of the same stage for dout [n][C][oh][ow], from the forward's r, g and h:
+ *   dg[n][C] = sum_hw dout * r;  dz = dg g (1 - g);  dh = (h > 0) w2^T dz;  dm = w1^T dh / (oh ow);
+ *   dr = dout * g[.., None, None] + dm[.., None, None]       dg [n][C], dr [n][C][oh][ow]. */
+int smc_irse_se_bwd_f32(const float* dout, const float* r, const float* g, const float* h, const float* w1,
+                        const float* w2, int n, int C, int hid, int oh, int ow, float* dg, float* dr, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * e4e / pSp encoder (encoder4editing/models/encoders/psp_encoders.py:58-200, helpers.py:123-140): the IR-SE50 trunk
  * with feature taps, the FPN's upsample-add and the grouped stride-2 convolution of the 18 map2style heads.

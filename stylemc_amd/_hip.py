@@ -157,6 +157,8 @@ _SIGS = {
     "smc_irse_workspace_bytes": (c_int64, [P, c_int]),
     "smc_irse_forward_f32": (c_int, [P, P, c_int, P, P, P, c_int64, P]),
     "smc_irse_backward_f32": (c_int, [P, P, c_int, c_int, P, P, P, c_int64, P]),
+    "smc_irse_se_fwd_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, P, P, P, P, P, P]),
+    "smc_irse_se_bwd_f32": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "smc_irse_trunk_workspace_bytes": (c_int64, [P, c_int]),
     "smc_irse_trunk_f32": (c_int, [P, P, c_int, P, P, c_int, P, c_int64, P]),
     "smc_upsample_add_f32": (c_int, [P, c_int64, c_int, c_int, P, P, c_int, c_int, P]),

@@ -400,6 +400,47 @@ smc_conv_epilogue epi_mode(int mode) {
         if (rc_ != SMC_OK) return rc_; \
     } while (0)
 
+// The two SE launch pairs of a unit (the executor and the stage entry points smc_irse_se_fwd_f32 / _bwd_f32 both go
+// through these, so neither can launch anything the other does not).
+// m = mean_hw(r); h = relu(W1 m); g = sigmoid(W2 h); out = r * g + shortcut (+ xbn = out * a + b): two launches
+int se_forward(const float* r, const float* sc, const float* x, int s, int in_h, int in_w, int n, int C, int oh, int ow,
+               const float* w1, const float* w2, int hid, const float* a, const float* b, float* out, float* xbn,
+               float* h, float* g, float* m, hipStream_t st) {
+    const int64_t ohw = (int64_t)oh * ow;
+    const int64_t planes = (int64_t)n * C;
+    hipLaunchKernelGGL(plane_dot_kernel<false>, dim3((unsigned)smc::ceil_div(planes, 4)), dim3(256), 0, st, r,
+                       (const float*)nullptr, m, planes, (int)ohw, 1.f / (float)ohw);
+    hipLaunchKernelGGL(se_fwd_combine_kernel, dim3(n, C / kSeCpb, se_zsplit(ohw)), dim3(256),
+                       sizeof(float) * (C + hid + 3 * kSeCpb), st, m, w1, w2, h, g, C, hid, r, sc, x, s, in_h, in_w, out,
+                       xbn, a, b, oh, ow);
+    return smc::check_launch("irse se + combine");
+}
+
+// dg = sum_hw dout * r; dm = SE chain; dr = dout * g + dm: two launches
+int se_backward(const float* dout, const float* r, const float* g, const float* h, const float* w1, const float* w2,
+                int n, int C, int hid, int64_t ohw, float* dg, float* dr, hipStream_t st) {
+    const int64_t planes = (int64_t)n * C;
+    hipLaunchKernelGGL(plane_dot_kernel<true>, dim3((unsigned)smc::ceil_div(planes, 4)), dim3(256), 0, st, dout, r, dg,
+                       planes, (int)ohw, 1.f);
+    hipLaunchKernelGGL(se_bwd_dr_kernel, dim3(n, C / kSeCpb, se_zsplit(ohw)), dim3(256),
+                       sizeof(float) * (C + hid + 2 * kSeCpb), st, dg, g, h, w1, w2, C, hid, 1.f / (float)ohw, dout, dr,
+                       ohw);
+    return smc::check_launch("irse se bwd");
+}
+
+// what trunk_validate requires of a unit's SE stage, for the stage entry points
+int se_validate(const char* who, int n, int C, int hid, int s, int in_h, int in_w) {
+    SMC_CHECK(n >= 1, "%s: batch %d", who, n);
+    SMC_CHECK(C >= kSeCpb && C % kSeCpb == 0, "%s: C %d not a multiple of %d", who, C, kSeCpb);
+    SMC_CHECK(C <= 64 * SE_MAXQ, "%s: C %d > %d", who, C, 64 * SE_MAXQ);
+    SMC_CHECK(hid >= 1 && hid <= 256, "%s: SE hidden width %d not in [1, 256]", who, hid);
+    SMC_CHECK(s == 1 || s == 2, "%s: stride %d", who, s);
+    SMC_CHECK(in_h >= s && in_w >= s && in_h % s == 0 && in_w % s == 0, "%s: odd size %d x %d at stride %d", who, in_h,
+              in_w, s);
+    SMC_CHECK((int64_t)(in_h / s) * (in_w / s) * n * C < (int64_t(1) << 31), "%s: tensor of 2^31 floats or more", who);
+    return SMC_OK;
+}
+
 // Stem and units of the forward (shared by smc_irse_forward_f32 and smc_irse_trunk_f32); *x_out = the last unit's
 // output.  The outputs of the units tap_units[0 .. ntaps) go to tap_out[.] instead of a workspace buffer.
 int forward_body(const smc_irse_net* net, const float* img, int n, float* saved, const Ws& w, void* stream,
@@ -437,7 +478,6 @@ int forward_body(const smc_irse_net* net, const float* img, int n, float* saved,
     for (int k = 0; k < net->n_units; ++k) {
         const smc_irse_unit& u = net->units[k];
         const int oh = u.in_h / u.stride, ow = u.in_w / u.stride;
-        const int64_t ohw = (int64_t)oh * ow;
         float* r = saved ? us[k].r : w.r;
         float* hbuf = saved ? us[k].h : w.h;
         float* gbuf = saved ? us[k].g : w.g;
@@ -451,10 +491,6 @@ int forward_body(const smc_irse_net* net, const float* img, int n, float* saved,
         e.scale_c = u.bn2_a;
         e.bias = u.bn2_b;
         SMC_TRY(conv(w.y1, u.depth, u.in_h, u.in_w, r, u.depth, oh, ow, &u.c2_fwd, 1, e));
-        // SE: m = mean_hw(r); h = relu(W1 m); g = sigmoid(W2 h)
-        const int64_t planes = (int64_t)n * u.depth;
-        hipLaunchKernelGGL(plane_dot_kernel<false>, dim3((unsigned)smc::ceil_div(planes, 4)), dim3(256), 0, st, r,
-                           (const float*)nullptr, w.m, planes, (int)ohw, 1.f / (float)ohw);
         // shortcut
         const float* sc = nullptr;
         if (u.sc_conv) {
@@ -469,11 +505,9 @@ int forward_body(const smc_irse_net* net, const float* img, int n, float* saved,
         for (int t = 0; t < ntaps; ++t)
             if (tap_units[t] == k) out = tap_out[t];  // a tapped unit writes its output into the caller's buffer
         const bool next = k + 1 < net->n_units;
-        hipLaunchKernelGGL(se_fwd_combine_kernel, dim3(n, u.depth / kSeCpb, se_zsplit(ohw)), dim3(256),
-                           sizeof(float) * (u.depth + u.se_hidden + 3 * kSeCpb), st, w.m, u.se_w1, u.se_w2, hbuf, gbuf,
-                           u.depth, u.se_hidden, r, sc, x, u.stride, u.in_h, u.in_w, out, next ? w.xbn : nullptr,
-                           next ? net->units[k + 1].bn1_a : nullptr, next ? net->units[k + 1].bn1_b : nullptr, oh, ow);
-        SMC_TRY(smc::check_launch("irse se + combine"));
+        SMC_TRY(se_forward(r, sc, x, u.stride, u.in_h, u.in_w, n, u.depth, oh, ow, u.se_w1, u.se_w2, u.se_hidden,
+                           next ? net->units[k + 1].bn1_a : nullptr, next ? net->units[k + 1].bn1_b : nullptr, out,
+                           next ? w.xbn : nullptr, hbuf, gbuf, w.m, st));
         x = out;
     }
     *x_out = x;
@@ -562,15 +596,10 @@ SMC_API int smc_irse_backward_f32(const smc_irse_net* net, const float* dfeat, i
         const smc_irse_unit& u = net->units[k];
         const int oh = u.in_h / u.stride, ow = u.in_w / u.stride;
         const int64_t ohw = (int64_t)oh * ow;
-        const int64_t planes = (int64_t)n * u.depth;
         const float* dout = dx;
         // SE + combine backward: dg = sum_hw dout * r; dm = SE chain; dr = dout * g + dm
-        hipLaunchKernelGGL(plane_dot_kernel<true>, dim3((unsigned)smc::ceil_div(planes, 4)), dim3(256), 0, st, dout,
-                           us[k].r, w.m, planes, (int)ohw, 1.f);
-        hipLaunchKernelGGL(se_bwd_dr_kernel, dim3(n, u.depth / kSeCpb, se_zsplit(ohw)), dim3(256),
-                           sizeof(float) * (u.depth + u.se_hidden + 2 * kSeCpb), st, w.m, us[k].g, us[k].h, u.se_w1,
-                           u.se_w2, u.depth, u.se_hidden, 1.f / (float)ohw, dout, w.r, ohw);
-        SMC_TRY(smc::check_launch("irse se bwd"));
+        SMC_TRY(se_backward(dout, us[k].r, us[k].g, us[k].h, u.se_w1, u.se_w2, n, u.depth, u.se_hidden, ohw, w.m, w.r,
+                            st));
         // du1 = PReLU'(u1) * conv2^T(dr)   (BN2 scale folded into the adjoint weights)
         smc_conv_epilogue e = epi_mode(SMC_EPI_PRELU_GRAD);
         e.alpha_c = u.prelu;
@@ -602,4 +631,24 @@ SMC_API int smc_irse_backward_f32(const smc_irse_net* net, const float* dfeat, i
     hipLaunchKernelGGL(channel_copy_kernel, dim3(ew_grid(tot)), dim3(256), 0, st, w.pad, net->stem_cin, dimg,
                        net->img_ch, hw0, tot);
     return smc::check_launch("irse unpad");
+}
+
+SMC_API int smc_irse_se_fwd_f32(const float* r, const float* sc, const float* x, int stride, int in_h, int in_w, int n,
+                                int C, const float* w1, const float* w2, int hid, const float* a, const float* b,
+                                float* out, float* xbn, float* h, float* g, float* m, void* stream) {
+    SMC_TRY(se_validate("smc_irse_se_fwd_f32", n, C, hid, stride, in_h, in_w));
+    SMC_CHECK(r && w1 && w2 && out && h && g && m, "smc_irse_se_fwd_f32: null pointer");
+    SMC_CHECK((sc != nullptr) != (x != nullptr), "smc_irse_se_fwd_f32: exactly one of sc and x");
+    SMC_CHECK(!xbn == !a && !xbn == !b, "smc_irse_se_fwd_f32: xbn, a and b go together");
+    return se_forward(r, sc, x, stride, in_h, in_w, n, C, in_h / stride, in_w / stride, w1, w2, hid, a, b, out, xbn, h,
+                      g, m, smc::as_stream(stream));
+}
+
+SMC_API int smc_irse_se_bwd_f32(const float* dout, const float* r, const float* g, const float* h, const float* w1,
+                                const float* w2, int n, int C, int hid, int oh, int ow, float* dg, float* dr,
+                                void* stream) {
+    SMC_CHECK(oh >= 1 && ow >= 1, "smc_irse_se_bwd_f32: plane %d x %d", oh, ow);
+    SMC_TRY(se_validate("smc_irse_se_bwd_f32", n, C, hid, 1, oh, ow));
+    SMC_CHECK(dout && r && g && h && w1 && w2 && dg && dr, "smc_irse_se_bwd_f32: null pointer");
+    return se_backward(dout, r, g, h, w1, w2, n, C, hid, (int64_t)oh * ow, dg, dr, smc::as_stream(stream));
 }
