@@ -321,6 +321,37 @@ int smc_modconv_up2_f32(const float* x, int n, int cin, int h, int w, float* y, 
 int smc_modconv_up2_last_route(void);
 const char* smc_modconv_up2_route_name(int route);
 
+/* A 32-channel synthesis block's conv1 and the ToRGB layer that reads its output, in one launch: the 3x3 Winograd
+ * F(2x2) conv of smc_conv3x3_wino_ws_f32 (same x, uw, s_in, epi) whose MODACT epilogue also forms
+ *   rgb[n, k, p] = clamp_rgb(sum_c w_rgb[k, c] * s_rgb[n, c] * y[n, c, p] + b_rgb[k])
+ * (the expression of smc_torgb_fwd_f32; replaces the same ToRGBLayer.forward call, utils.py:47) from the fp32 y values
+ * in its registers.  rgb: [n, cout_rgb, h, w]; w_rgb: [cout_rgb, cout]; s_rgb: [n, cout]; b_rgb: [cout_rgb] or NULL.
+ * y: [n, cout, h, w], bit-identical to the unsplit smc_conv3x3_wino_ws_f32 launch of the same style form -- or NULL,
+ * and only rgb is written (a block whose output nothing else reads).  The dot product is one FMA chain over the
+ * channels in ascending order at every plane size, so a launch is bit-reproducible; on planes above 4096 positions that
+ * is smc_torgb_fwd_f32's order and rgb is bit-identical to it (its small-plane kernel sums in another order).
+ * smc_modconv_conv1_torgb_supported(): cout == 32, cout_rgb in 1..4, a shape smc_conv3x3_wino_supported() accepts
+ * that the two-launch path runs in one pass at the planning batch (no split-K), and -- where epi is not NULL -- the
+ * MODACT lrelu epilogue (0 <= alpha <= 1, clamp >= 0) without u_save or residual (epi NULL asks about the shape
+ * alone).  Anything else returns SMC_ERR_UNSUPPORTED and the caller keeps the two launches; so does the launch with
+ * epi NULL, the STORE default of smc_conv3x3_wino_ws_f32, which has no fused form.
+ * `workspace`: smc_modconv_conv1_torgb_workspace_size() bytes (16-B aligned) hold the per-image taps with s_in folded
+ * in (the launch then runs the SM = 2 form, as SMC_ROUTE_WINO_FOLD of smc_conv3x3_wino_ws_f32); without it the style
+ * scale is applied in the kernel (SM = 1).
+ * Route report of the last call of this thread: 0 ("none") when it failed before its launch, else
+ * wino_rgb_kernel<TC,SM> by smc_modconv_conv1_torgb_route_name (NULL outside 0 .. route_count() - 1).
+ * Added under ABI version 6 without a version bump: callers detect these entry points by symbol. */
+int smc_modconv_conv1_torgb_supported(int n, int cin, int cout, int h, int w, int cout_rgb,
+                                      const smc_conv_epilogue* epi);
+int64_t smc_modconv_conv1_torgb_workspace_size(int n, int cin, int cout, int h, int w);
+int smc_modconv_conv1_torgb_f32(const float* x, int n, int cin, int h, int w, float* y, int cout, const float* uw,
+                                const float* s_in, const smc_conv_epilogue* epi, const float* w_rgb,
+                                const float* s_rgb, const float* b_rgb, float clamp_rgb, int cout_rgb, float* rgb,
+                                float* workspace, int64_t workspace_bytes, void* stream);
+int smc_modconv_conv1_torgb_last_route(void);
+int smc_modconv_conv1_torgb_route_count(void);
+const char* smc_modconv_conv1_torgb_route_name(int route);
+
 /* Backward of smc_modconv_blur_act_f32 in one pass: du = bias_act'(g; y re-derived from u) * d[n,o],
  * dt = adjoint FIR of du (pad (pady0, padx0) = (fh-1-p, fw-1-p) of the forward pad p, flip, gain fgain;
  * upfirdn2d.py:245-264 rule), and if dd != NULL: dd[n,o] += sum_hw dz*u.  g/u: [n,c,u_h,u_w],

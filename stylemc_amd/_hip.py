@@ -106,6 +106,13 @@ _SIGS = {
                                     P, c_int64, P]),
     "smc_modconv_up2_last_route": (c_int, []),
     "smc_modconv_up2_route_name": (c_char_p, [c_int]),
+    "smc_modconv_conv1_torgb_supported": (c_int, [c_int] * 6 + [P]),
+    "smc_modconv_conv1_torgb_workspace_size": (c_int64, [c_int] * 5),
+    "smc_modconv_conv1_torgb_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, c_float, c_int,
+                                            P, P, c_int64, P]),
+    "smc_modconv_conv1_torgb_last_route": (c_int, []),
+    "smc_modconv_conv1_torgb_route_count": (c_int, []),
+    "smc_modconv_conv1_torgb_route_name": (c_char_p, [c_int]),
     "smc_modconv_blur_act_bwd_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int,
                                              c_int, c_int, c_int, c_float, c_int, P, P, c_int64, P]),
     "smc_modconv_blur_act_bwd_workspace_size": (c_int64, [c_int] * 6),

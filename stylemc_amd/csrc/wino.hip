@@ -77,6 +77,18 @@ struct WinoParams {
     int64_t u_nstride;     // 0: one U for the batch; else floats between per-image U (s[n, c] folded in)
 };
 
+// ToRGB operands of the fused conv1 + ToRGB launch (wino_rgb_kernel; cout = 32, so a workgroup holds every channel of
+// its pixels): rgb[n, k, p] = clamp(sum_c w[k, c] s[n, c] y[n, c, p] + b[k]), smc_torgb_fwd_f32's expression.
+struct WinoRgb {
+    const float* w;   // [krgb][32]
+    const float* s;   // [n][32]
+    const float* b;   // [krgb] or NULL
+    float clamp;
+    int krgb;         // 1 .. 4 image channels
+    float* rgb;       // [n][krgb][h][w]
+};
+constexpr int WRGB = 4;   // image channels at most (smc_torgb_fwd_f32's limit)
+
 // Staged row pitch: CHP >= CH 16-B chunks (the pad chunks are sentinel DMA lanes, zero-filled) so that a channel slab
 // is 32 floats mod 64.  A lane reads its 4 x 4 patch as three aligned 8-B reads per row (columns 2 tc + 2 .. + 7 of
 // the staged row); in a read group the 16 tiles' pairs of one channel cover 32 consecutive dwords and the other
@@ -126,9 +138,12 @@ struct WinoItem {
 // instead of starting every workgroup cold -- what the 4-step (cin 32) and 8-step (cin 64) layers lost most to.
 // EK: the epilogue body, chosen at launch (1: MODACT lrelu + gain + clamp, 2: MODACT linear, 0: any mode, 3: the raw
 // output tiles of a K split into the workspace -- the split-K form, p.nsplit > 1, grid.y = split).
-template <int TC, int SM, int EK, int PERSIST, int PROBE = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void wino_kernel(WinoParams p) {
+// The work-item loop (K loop, output transform, epilogue) is this one device function, shared by wino_kernel and
+// wino_rgb_kernel.  RGB (EK 1, cout = 32, no u_save): the epilogue also forms the ToRGB image rg.rgb from the y values
+// in its registers, and stores y only where p.y is set.
+template <int TC, int SM, int EK, int PERSIST, int PROBE, int RGB>
+__device__ __forceinline__ void wino_items(const WinoParams& p, const WinoRgb& rg) {
+    static_assert(!RGB || (EK == 1 && !PERSIST && !PROBE), "the ToRGB epilogue extends the MODACT lrelu form");
     using C = WinoCfg<TC>;
     constexpr int OBW = 2, NW = C::NW, UJW = C::UJW, PJW = C::PJW;
     constexpr int TR = C::TR, ROWS = C::ROWS, CH = C::CH, CHP = C::CHP, PITCH = C::PITCH, SLAB = C::SLAB;
@@ -398,6 +413,8 @@ void wino_kernel(WinoParams p) {
                             nz[i][j] = p.noise[nn * p.noise_nstride + (int64_t)(yy0 + i) * W + xx0 + j] * nstr;
                 }
             }
+            // ToRGB: the lane keeps the y values of its 8 channels x 2x2 pixels for the exchange after the body
+            float yv[RGB ? OBW * 4 : 1][2][2];
             // The synthesis' two MODACT forms get a body with the activation fixed at compile time (KIND 1: lrelu
             // with 0 <= alpha <= 1, gain, clamp -- the conv1 forward; KIND 2: linear, no clamp -- the data gradient's
             // x s[n, i]): lrelu(z) = max(z, alpha z) and clamp = min / max, bit-identical to smc::epi_y for every
@@ -437,8 +454,9 @@ void wino_kernel(WinoParams p) {
 #pragma unroll
                             for (int i = 0; i < 2; ++i) {
                                 const int64_t idx = obase + (int64_t)(yy0 + i) * W + xx0;
-                                if (p.u_save)
-                                    *reinterpret_cast<float2*>(p.u_save + idx) = make_float2(out[i][0], out[i][1]);
+                                if constexpr (!RGB)
+                                    if (p.u_save)
+                                        *reinterpret_cast<float2*>(p.u_save + idx) = make_float2(out[i][0], out[i][1]);
                                 float q[2];
 #pragma unroll
                                 for (int j = 0; j < 2; ++j) {
@@ -454,7 +472,13 @@ void wino_kernel(WinoParams p) {
                                                                       xx0 + j, p.cout, H, W, nullptr, nullptr, p.ext);
                                     }
                                 }
-                                *reinterpret_cast<float2*>(p.y + idx) = make_float2(q[0], q[1]);
+                                if constexpr (RGB) {
+                                    yv[4 * b + r][i][0] = q[0];
+                                    yv[4 * b + r][i][1] = q[1];
+                                    if (p.y) *reinterpret_cast<float2*>(p.y + idx) = make_float2(q[0], q[1]);
+                                } else {
+                                    *reinterpret_cast<float2*>(p.y + idx) = make_float2(q[0], q[1]);
+                                }
                             }
                         } else {
 #pragma unroll
@@ -472,6 +496,54 @@ void wino_kernel(WinoParams p) {
                 }
             };
             body(std::integral_constant<int, EK>{});
+            if constexpr (RGB) {
+                // The tile's 32 channels sit in the four lanes l, l ^ 16, l ^ 32, l ^ 48 (k-quad kq = lane >> 4 holds
+                // channels 16 b + 4 kq + r), each with the tile's 2x2 pixels.  Two exchanges transpose that 4 x 4: the
+                // half-wave swap leaves pixel row i = lane >> 5 of k-quads kq & 1 and (kq & 1) + 2 in each lane, the
+                // 16-lane row swap then column j = (lane >> 4) & 1 of all four k-quads -- one pixel, 32 channels per
+                // lane, 32 swaps, no LDS, no barrier.  The dot then runs over the channels in ascending order as one
+                // FMA chain from zero: the order (and the bits) of torgb_fwd_kernel's per-position loop.
+                float qv[4][OBW * 4];   // [k-quad][4 b + r]
+#pragma unroll
+                for (int c8 = 0; c8 < OBW * 4; ++c8) {
+                    unsigned h[2][2];   // [k-quad pair member m: k-quad (kq & 1) + 2 m][j]
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        // rows 2, 3 of the first operand <-> rows 0, 1 of the second
+                        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(yv[c8][0][j]),
+                                                                         __float_as_uint(yv[c8][1][j]), false, false);
+                        h[0][j] = sw[0];
+                        h[1][j] = sw[1];
+                    }
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) {
+                        // odd rows of the first operand <-> even rows of the second
+                        const auto sw = __builtin_amdgcn_permlane16_swap(h[m][0], h[m][1], false, false);
+                        qv[2 * m][c8] = __uint_as_float(sw[0]);
+                        qv[2 * m + 1][c8] = __uint_as_float(sw[1]);
+                    }
+                }
+                // w, s, b are read-only for the whole launch: through the constant address space the wave-uniform
+                // loads stay scalar after the y stores above
+                typedef const float __attribute__((address_space(4)))* cf32p;
+                const cf32p wc = (cf32p)rg.w, sc = (cf32p)rg.s + (int64_t)nn * WBO, bc = (cf32p)rg.b;
+                const int64_t pix = (int64_t)(yy0 + (lane >> 5)) * W + xx0 + ((lane >> 4) & 1);
+#pragma unroll
+                for (int k = 0; k < WRGB; ++k) {
+                    if (k >= rg.krgb) break;
+                    float t = 0.f;
+#pragma unroll
+                    for (int b = 0; b < OBW; ++b)
+#pragma unroll
+                        for (int kq = 0; kq < 4; ++kq)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const int o = 16 * b + 4 * kq + r;
+                                t = __fmaf_rn(wc[k * WBO + o] * sc[o], qv[kq][4 * b + r], t);
+                            }
+                    rg.rgb[((int64_t)nn * rg.krgb + k) * plane + pix] = smc::clamp_fwd(t + (bc ? bc[k] : 0.f), rg.clamp);
+                }
+            }
         }
         if (!has_next) break;
         v = vn;
@@ -479,6 +551,19 @@ void wino_kernel(WinoParams p) {
         offsets(it, uv, pv);  // (recomputed: cheaper than keeping the next item's offsets alive through the epilogue)
         srow = srow_n;
     }
+}
+
+template <int TC, int SM, int EK, int PERSIST, int PROBE = 0>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void wino_kernel(WinoParams p) {
+    wino_items<TC, SM, EK, PERSIST, PROBE, 0>(p, WinoRgb{});
+}
+
+// conv1 + ToRGB of a 32-channel block in one launch: the MODACT lrelu epilogue (EK 1) that also writes the image
+template <int TC, int SM>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void wino_rgb_kernel(WinoParams p, WinoRgb rg) {
+    wino_items<TC, SM, 1, 0, 0, 1>(p, rg);
 }
 
 // Per-image U with the style folded in: out[nn][c][...] = uw[c][...] * s[nn][c] (float4 runs of the [cin][4][cout][4]
@@ -1124,4 +1209,112 @@ SMC_API int smc_conv3x3_wino_route_count(void) { return kWinoRouteCount; }
 
 SMC_API const char* smc_conv3x3_wino_route_name(int route) {
     return route >= 0 && route < kWinoRouteCount ? kWinoRouteNames[route] : nullptr;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// conv1 + ToRGB of a 32-channel synthesis block in one launch (wino_rgb_kernel): the block's last conv and the 1x1
+// ToRGB that reads its output, with y stored only where the caller needs it.  A route report of its own.
+namespace {
+
+constexpr const char* kWinoRgbRouteNames[] = {
+    "none", "wino_rgb_kernel<32,1>", "wino_rgb_kernel<32,2>", "wino_rgb_kernel<16,1>", "wino_rgb_kernel<16,2>",
+};
+constexpr int kWinoRgbRouteCount = sizeof(kWinoRgbRouteNames) / sizeof(kWinoRgbRouteNames[0]);
+constexpr int wino_rgb_route(int tc, int sm) { return 1 + (tc == 32 ? 0 : 2) + (sm - 1); }
+thread_local int g_wino_rgb_route = 0;
+
+template <int TC, int SM>
+void launch_wino_rgb(const WinoParams& p, const WinoRgb& rg, int64_t items, hipStream_t st) {
+    g_wino_rgb_route = wino_rgb_route(TC, SM);
+    hipLaunchKernelGGL((wino_rgb_kernel<TC, SM>), dim3((unsigned)items), dim3(256), 0, st, p, rg);
+}
+
+// the epilogue the fused kernel computes: conv1's MODACT lrelu + gain + clamp (wino_kernel's EK 1), no u_save
+bool wino_rgb_epi_ok(const smc_conv_epilogue* e) {
+    if (!e) return true;
+    const smc::EpiExt ext = smc::epi_ext(e);
+    return e->mode == SMC_EPI_MODACT && !ext.residual && e->act == SMC_ACT_LRELU && e->alpha >= 0.f && e->alpha <= 1.f &&
+           e->clamp >= 0.f && !e->u_save;
+}
+
+}  // namespace
+
+SMC_API int smc_modconv_conv1_torgb_supported(int n, int cin, int cout, int h, int w, int cout_rgb,
+                                              const smc_conv_epilogue* epi) {
+    if (cout != WBO || cout_rgb < 1 || cout_rgb > WRGB) return 0;
+    if (!smc_conv3x3_wino_supported(n, cin, cout, h, w)) return 0;
+    // one pass: where the two-launch path plans split-K (or the experimental split-bf16 kernel is on) it keeps the call
+    if (wino_nsplit(n, cin, cout, h, w) != 1 || wino_x3_bytes(n, cin, cout, h, w) > 0) return 0;
+    return wino_rgb_epi_ok(epi) ? 1 : 0;
+}
+
+// [per-image folded U]: with it the launch runs the folded form (SM 2), without it the style scale in the kernel (SM 1)
+SMC_API int64_t smc_modconv_conv1_torgb_workspace_size(int n, int cin, int cout, int h, int w) {
+    if (!smc_modconv_conv1_torgb_supported(n, cin, cout, h, w, 1, nullptr)) return 0;
+    return SMC_WINO_FOLD ? wino_fold_bytes(n, cin, cout) : 0;
+}
+
+SMC_API int smc_modconv_conv1_torgb_f32(const float* x, int n, int cin, int h, int w, float* y, int cout,
+                                        const float* uw, const float* s_in, const smc_conv_epilogue* epi,
+                                        const float* w_rgb, const float* s_rgb, const float* b_rgb, float clamp_rgb,
+                                        int cout_rgb, float* rgb, float* workspace, int64_t workspace_bytes,
+                                        void* stream) {
+    g_wino_rgb_route = 0;
+    SMC_CHECK(x && uw, "smc_modconv_conv1_torgb_f32: null pointer (x, uw)");
+    SMC_CHECK(rgb && w_rgb && s_rgb, "smc_modconv_conv1_torgb_f32: null pointer (rgb, w_rgb, s_rgb)");
+    // (a NULL epi is the STORE default of smc_conv3x3_wino_ws_f32: no fused form; the predicate takes NULL to ask about
+    // the shape alone)
+    if (!epi || !smc_modconv_conv1_torgb_supported(n, cin, cout, h, w, cout_rgb, epi)) {
+        smc::set_error("smc_modconv_conv1_torgb_f32: no fused kernel for n=%d cin=%d cout=%d %dx%d cout_rgb=%d with "
+                       "this epilogue", n, cin, cout, h, w, cout_rgb);
+        return SMC_ERR_UNSUPPORTED;
+    }
+    SMC_CHECK((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0 &&
+                  (reinterpret_cast<uintptr_t>(uw) & 15) == 0 && (reinterpret_cast<uintptr_t>(rgb) & 3) == 0,
+              "smc_modconv_conv1_torgb_f32: x / uw must be 16-B, y 8-B and rgb 4-B aligned");
+    WinoParams p{};
+    p.x = x; p.n = n; p.cin = cin; p.h = h; p.w = w; p.y = y; p.cout = cout; p.uw = uw; p.s = s_in;
+    p.mode = epi->mode; p.d = epi->d; p.noise = epi->noise; p.noise_nstride = epi->noise_nstride;
+    p.noise_strength = epi->noise_strength; p.bias = epi->bias; p.act = epi->act; p.alpha = epi->alpha;
+    p.gain = epi->gain; p.clamp = epi->clamp;
+    p.ext = smc::epi_ext(epi);
+    const int tc = wino_tc(h, w);
+    p.gx = (w / 2) / tc;
+    p.gy = (h / 2) / (WBT / tc);
+    p.ntn = 1;
+    p.nsplit = 1;
+    const int64_t items = (int64_t)n * p.gx * p.gy;
+    SMC_CHECK(items < (1LL << 31), "smc_modconv_conv1_torgb_f32: grid too large");
+    WinoRgb rg{w_rgb, s_rgb, b_rgb, clamp_rgb, cout_rgb, rgb};
+    hipStream_t st = smc::as_stream(stream);
+    const int64_t fold_bytes = smc_modconv_conv1_torgb_workspace_size(n, cin, cout, h, w);
+    if (s_in && fold_bytes > 0 && workspace && workspace_bytes >= fold_bytes) {
+        SMC_CHECK((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "smc_modconv_conv1_torgb_f32: workspace alignment");
+        const int per4 = cin * 4 * cout;   // float4 per image
+        const int64_t total4 = (int64_t)n * per4;
+        hipLaunchKernelGGL(wino_ufold_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(total4, 256), 4096)),
+                           dim3(256), 0, st, reinterpret_cast<const float4*>(uw), s_in,
+                           reinterpret_cast<float4*>(workspace), cin, per4, total4);
+        const int rc = smc::check_launch("smc_modconv_conv1_torgb_f32 (style fold)");
+        if (rc != SMC_OK) return rc;
+        p.uw = workspace;
+        p.u_nstride = (int64_t)cin * 16 * cout;
+        p.s = nullptr;
+    }
+    if (p.s) {
+        if (tc == 32) launch_wino_rgb<32, 1>(p, rg, items, st);
+        else launch_wino_rgb<16, 1>(p, rg, items, st);
+    } else {
+        if (tc == 32) launch_wino_rgb<32, 2>(p, rg, items, st);
+        else launch_wino_rgb<16, 2>(p, rg, items, st);
+    }
+    return smc::check_launch("smc_modconv_conv1_torgb_f32");
+}
+
+SMC_API int smc_modconv_conv1_torgb_last_route(void) { return g_wino_rgb_route; }
+
+SMC_API int smc_modconv_conv1_torgb_route_count(void) { return kWinoRgbRouteCount; }
+
+SMC_API const char* smc_modconv_conv1_torgb_route_name(int route) {
+    return route >= 0 && route < kWinoRgbRouteCount ? kWinoRgbRouteNames[route] : nullptr;
 }

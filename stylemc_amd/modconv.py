@@ -292,6 +292,39 @@ def fused_up(x, y, phases, nph, cin, cout, s, epi, alg_flops=0.0, alg_bytes=0):
         tm.finish(tok)
 
 
+# A 32-channel block's conv1 and its ToRGB in one launch, smc_modconv_conv1_torgb_f32 (the last FFHQ-1024 block: the
+# Winograd epilogue forms the image from the y values in its registers, so ToRGB's pass over y goes, and y itself is
+# not stored where nothing reads it).  Module switch, as FUSED_UP.
+FUSED_TORGB = True
+
+
+def fused_torgb_ok(spec, n, cin, h, w, cout_rgb, epi, has_u):
+    """Whether conv1 + ToRGB take the fused launch: a 3x3 layer on the F(2x2) path (not F(4x4)), no saved u (the style
+    gradient's layers keep the two launches), and the library's gate -- 32 output channels, 1..4 image channels, the
+    lrelu epilogue, and a two-launch plan that runs unsplit at the planning batch."""
+    P = spec.packed
+    if not (FUSED_TORGB and spec.up == 1 and P.k == 3 and not has_u):
+        return False
+    if wino4_pick(n, cin, P.cout, h, w) or not wino_ok(n, cin, P.cout, h, w):
+        return False
+    return bool(_hip.load().smc_modconv_conv1_torgb_supported(n, cin, P.cout, h, w, cout_rgb, ctypes.byref(epi)))
+
+
+def fused_torgb(x, y, uw, cin, cout, s, epi, s_rgb, w_rgb, b_rgb, clamp_rgb, rgb, alg_flops=0.0, alg_bytes=0):
+    """One smc_modconv_conv1_torgb_f32 launch (y None: only rgb is written).  Timed as a Winograd launch: alg_flops
+    the conv's MFMA FLOPs, alg_bytes what it really moves."""
+    n, _, h, w = x.shape
+    ws_bytes = _hip.load().smc_modconv_conv1_torgb_workspace_size(n, cin, cout, h, w) if WINO_SPLIT else 0
+    ws = torch.empty(ws_bytes // 4, device=x.device, dtype=torch.float32) if ws_bytes > 0 else None
+    tm = _hip.timer()
+    tok = tm.wrap(alg_flops, alg_bytes, kind="wino", equiv_flops=alg_flops * 36 / 16) if tm is not None else None
+    _hip.call("smc_modconv_conv1_torgb_f32", x.data_ptr(), n, cin, h, w, _hip.ptr(y), cout, uw.data_ptr(), _hip.ptr(s),
+              ctypes.byref(epi), w_rgb.data_ptr(), s_rgb.data_ptr(), _hip.ptr(b_rgb), clamp_rgb, w_rgb.shape[0],
+              rgb.data_ptr(), _hip.ptr(ws), ws_bytes, _hip.stream())
+    if tok is not None:
+        tm.finish(tok)
+
+
 def _epilogue(mode, d=None, noise=None, noise_nstride=0, strength=None, bias=None, act="linear", alpha=0.0,
               gain=1.0, clamp=-1.0, u_save=None):
     e = _hip.ConvEpilogue()
@@ -356,9 +389,12 @@ def _noise_args(noise):
     return noise, noise.shape[2] * noise.shape[3]
 
 
-def _modconv_fwd(ctx, x, styles, spec, noise, strength, gain, clamp, need_dx, need_ds):
+def _modconv_fwd(ctx, x, styles, spec, noise, strength, gain, clamp, need_dx, need_ds, torgb=None):
     """The modconv forward (GEMM + fused epilogue); sets ctx's backward state, returns y and the tensors the
-    backward needs (x, styles, d, and u -- or y itself where the styles need no gradient)."""
+    backward needs (x, styles, d, and u -- or y itself where the styles need no gradient).
+    torgb = (s_rgb, w_rgb, b_rgb, clamp_rgb, need_y): the ToRGB layer reading y; the return gains a third value, its
+    image where the fused conv1 + ToRGB launch took the layer (else None: the caller runs ToRGB), and with no gradient
+    saved and need_y False that launch stores no y (y is None)."""
     x = x.contiguous()
     styles = styles.contiguous()
     P = spec.packed
@@ -374,13 +410,26 @@ def _modconv_fwd(ctx, x, styles, spec, noise, strength, gain, clamp, need_dx, ne
     # the activation mask of the backward needs only y; u is kept only where the style gradient needs
     # dd = sum dz * u (the trainable layers): every other layer skips the u store (grad_from_y backward)
     from_y = save and not need_ds
-    y = torch.empty(n, P.cout, r_h, r_w, device=x.device, dtype=torch.float32)
-    u = torch.empty_like(y) if save and not from_y else None
+    has_u = save and not from_y
     nz, nstride = _noise_args(noise)
-    epi = _epilogue(_hip.EPI_MODACT, d, nz, nstride, strength, spec.bias, spec.act, spec.alpha, gain, clamp, u)
+    epi = _epilogue(_hip.EPI_MODACT, d, nz, nstride, strength, spec.bias, spec.act, spec.alpha, gain, clamp)
+    rgb = None
+    fuse_rgb = torgb is not None and fused_torgb_ok(spec, n, cin, h, w, torgb[1].shape[0], epi, has_u)
+    if fuse_rgb and not save and not torgb[4]:
+        y = None
+    else:
+        y = torch.empty(n, P.cout, r_h, r_w, device=x.device, dtype=torch.float32)
+    u = torch.empty_like(y) if has_u else None
+    epi.u_save = _hip.ptr(u)
     phases, nph, th, tw = P.fwd_phases(h, w)
     wbytes = 4 * P.k * P.k * cin * P.cout
-    if spec.up == 1 and P.k == 3 and wino4_pick(n, cin, P.cout, h, w):
+    if fuse_rgb:
+        s_rgb, w_rgb, b_rgb, clamp_rgb = torgb[:4]
+        rgb = torch.empty(n, w_rgb.shape[0], r_h, r_w, device=x.device, dtype=torch.float32)
+        fused_torgb(x, y, P.wino_weights(0), cin, P.cout, styles, epi, s_rgb, w_rgb, b_rgb, clamp_rgb, rgb,
+                    alg_flops=wino_flops(n, cin, P.cout, h, w),
+                    alg_bytes=4 * x.numel() + _nbytes(y) + 4 * rgb.numel() + 16 * 4 * cin * P.cout)
+    elif spec.up == 1 and P.k == 3 and wino4_pick(n, cin, P.cout, h, w):
         wino4(x, y, P.wino4_weights(0), cin, P.cout, s=styles, epi=epi, alg_flops=wino4_flops(n, cin, P.cout, h, w),
               alg_bytes=4 * x.numel() + 4 * y.numel() * (2 if u is not None else 1) + 36 * 4 * cin * P.cout)
     elif spec.up == 1 and P.k == 3 and wino_ok(n, cin, P.cout, h, w):
@@ -405,7 +454,8 @@ def _modconv_fwd(ctx, x, styles, spec, noise, strength, gain, clamp, need_dx, ne
     ctx.spec, ctx.gain, ctx.clamp = spec, gain, clamp
     ctx.noise, ctx.nstride, ctx.strength = nz, nstride, strength
     ctx.from_y = from_y
-    return y, (x, styles, d, y if from_y else u)
+    saved = (x, styles, d, y if from_y else u)
+    return (y, saved) if torgb is None else (y, saved, rgb)
 
 
 def _modconv_epi_bwd(ctx, d):
@@ -537,15 +587,25 @@ class ModConvToRGBFn(torch.autograd.Function):
     returns (y, rgb).  y also feeds the next block's conv0, so its gradient is g_next + ToRGB^T(g_rgb); where
     conv1's styles need no gradient the backward forms it and conv1's epilogue backward in one pass
     (smc_torgb_act_bwd_f32) instead of a ToRGB data-gradient kernel, autograd's sum and the act backward
-    (utils.py:47 + [upstream] SynthesisBlock.forward; same numbers bit for bit)."""
+    (utils.py:47 + [upstream] SynthesisBlock.forward; same numbers bit for bit).
+    A 32-channel conv1 on the F(2x2) path takes both layers in one launch (FUSED_TORGB, fused_torgb_ok): same y, the
+    image summed in that kernel's fixed order.  need_y=False (the last synthesised block, whose y nobody reads):
+    where that launch runs and no input of the Function (x, conv1's styles, the ToRGB styles) requires a gradient, y
+    is neither allocated nor stored and the Function returns (None, rgb).  The saved tensors and the backward are the same either way."""
 
     @staticmethod
-    def forward(ctx, x, styles, spec, noise, strength, gain, clamp, s_rgb, w_rgb, b_rgb, clamp_rgb):
+    def forward(ctx, x, styles, spec, noise, strength, gain, clamp, s_rgb, w_rgb, b_rgb, clamp_rgb, need_y=True):
         ctx.set_materialize_grads(False)
-        y, saved = _modconv_fwd(ctx, x, styles, spec, noise, strength, gain, clamp, ctx.needs_input_grad[0],
-                                ctx.needs_input_grad[1])
         s_rgb = s_rgb.contiguous()
-        rgb = _torgb_fwd(y, s_rgb, w_rgb, b_rgb, clamp_rgb)
+        # y may go only where no input of the Function needs a gradient: the ToRGB style gradient (input 7) reads the
+        # saved y too, also where x and conv1's styles need none
+        keep_y = need_y or any(ctx.needs_input_grad)
+        y, saved, rgb = _modconv_fwd(ctx, x, styles, spec, noise, strength, gain, clamp, ctx.needs_input_grad[0],
+                                     ctx.needs_input_grad[1], torgb=(s_rgb, w_rgb, b_rgb, clamp_rgb, keep_y))
+        if rgb is None:
+            rgb = _torgb_fwd(y, s_rgb, w_rgb, b_rgb, clamp_rgb)
+        if y is None:   # need_y False and no input needs a gradient: the fused launch stored the image alone
+            return None, rgb
         ctx.clamp_rgb = clamp_rgb
         ctx.save_for_backward(*saved, y, s_rgb, w_rgb, rgb)
         return y, rgb
@@ -575,7 +635,7 @@ class ModConvToRGBFn(torch.autograd.Function):
                               s_rgb.data_ptr(), gtot.data_ptr(), n, c, w_rgb.shape[0], h, w, ctx.clamp_rgb, 1, 1,
                               _hip.stream())
                 dx, ds = _modconv_bwd(ctx, saved, gtot, need_dx, need_ds)
-        return dx, ds, None, None, None, None, None, ds_rgb, None, None, None
+        return dx, ds, None, None, None, None, None, ds_rgb, None, None, None, None
 
 
 class ToRGBFn(torch.autograd.Function):

@@ -173,12 +173,13 @@ class SynthesisBlock(torch.nn.Module):
         self.torgb = ToRGBLayer(out_channels, img_channels, w_dim, conv_clamp=conv_clamp)
         self.num_torgb += 1
 
-    def conv1_torgb(self, x, w1, w_rgb, noise_mode="random", rgb_scaled=False):
+    def conv1_torgb(self, x, w1, w_rgb, noise_mode="random", rgb_scaled=False, need_y=True):
         """conv1(x, w1) and the ToRGB of its output as one autograd Function (modconv.ModConvToRGBFn, whose
         backward fuses the two gradients of the block output): returns (x, rgb) = (conv1 output, ToRGB output).
-        rgb_scaled: w_rgb is already the ToRGB styles (affine(w_rgb) * weight_gain, see utils._gather_rows)."""
+        rgb_scaled: w_rgb is already the ToRGB styles (affine(w_rgb) * weight_gain, see utils._gather_rows).
+        need_y=False: the caller reads only rgb (the last synthesised block); x may then come back as None."""
         return modconv.ModConvToRGBFn.apply(*self.conv1.fn_args(x, w1, noise_mode),
-                                            *self.torgb.fn_args(x, w_rgb, scaled=rgb_scaled)[1:])
+                                            *self.torgb.fn_args(x, w_rgb, scaled=rgb_scaled)[1:], need_y)
 
     def forward(self, x, img, ws, force_fp32=False, fused_modconv=None, **layer_kwargs):
         rows = iter(ws.unbind(dim=1))

@@ -139,6 +139,7 @@ def generate_image_rows(G, until_k, styles, temp_shapes, noise_mode="const", del
     edited = None
     if block is not None:
         edited = (block + delta.reshape(-1, len(trainable), block.shape[2]).transpose(0, 1)).unbind(0)
+    last_k = min(until_k, len(G.synthesis.block_resolutions) - 1)
     for k, res in enumerate(G.synthesis.block_resolutions):
         if k > until_k:
             continue
@@ -162,8 +163,10 @@ def generate_image_rows(G, until_k, styles, temp_shapes, noise_mode="const", del
             img = upfirdn2d.upsample2d(img, block_k.resample_filter)
         # conv1 + ToRGB as one Function: the backward sums the block output's two gradients (ToRGB and the next
         # block's conv0) inside conv1's epilogue backward
+        # (the last synthesised block's x has no reader: need_y=False lets its conv1 skip the store)
         x, y = block_k.conv1_torgb(x, w1, rows[-1][..., :shapes[2]], noise_mode=noise_mode,
-                                   rgb_scaled=rgb_prescaled and ((row + width - 1) not in trainable or delta is None))
+                                   rgb_scaled=rgb_prescaled and ((row + width - 1) not in trainable or delta is None),
+                                   need_y=k < last_k)
         img = img.add_(y) if img is not None else y
         row += width
     return img
