@@ -242,6 +242,13 @@ int smc_conv3x3_wino_last_route_flags(void);
 int smc_conv3x3_wino_last_nsplit(void);
 int smc_conv3x3_wino_route_count(void);
 const char* smc_conv3x3_wino_route_name(int route);
+/* The plan of a smc_conv3x3_wino_ws_f32 call, without the call (host only, no device call): the route, flags and K
+ * splits that a call of this shape would report, with a style scale or not (has_style), this epilogue (NULL: the plain
+ * store) and a workspace of workspace_bytes (0: none).  Of epi only the fields are read, no memory behind its
+ * pointers.  Returns SMC_ERR_UNSUPPORTED (route 0) where smc_conv3x3_wino_supported() is 0.  Any of route, flags,
+ * nsplit may be NULL.  Added under ABI version 6 without a version bump, as the route report. */
+int smc_conv3x3_wino_plan(int n, int cin, int cout, int h, int w, int has_style, const smc_conv_epilogue* epi,
+                          int64_t workspace_bytes, int* route, int* flags, int* nsplit);
 /* Experimental split-bf16 F(2x2) for cin = cout = 32, w % 64 == 0, h % 4 == 0 (the r = 1024 conv1), taken by
  * smc_conv3x3_wino_ws_f32 with its workspace when enabled: mode 0 off (the default: slower in the full step,
  * profiles/r06/wino_x3/README), 1 for the MODACT lrelu form, 2 also for the linear form.  Process-wide; returns the
@@ -267,6 +274,10 @@ int smc_conv3x3_wino4_f32(const float* x, int n, int cin, int h, int w, float* y
 int smc_conv3x3_wino4_last_route(void);
 int smc_conv3x3_wino4_route_count(void);
 const char* smc_conv3x3_wino4_route_name(int route);
+/* The plan of a smc_conv3x3_wino4_f32 call, as smc_conv3x3_wino_plan: the route it would report (SM by has_style, EK
+ * by epi); SMC_ERR_UNSUPPORTED (route 0) where smc_conv3x3_wino4_supported() is 0.  Host only. */
+int smc_conv3x3_wino4_plan(int n, int cin, int cout, int h, int w, int has_style, const smc_conv_epilogue* epi,
+                           int* route);
 /* w [cout][cin][3][3] -> uw [K][9][N][4] floats (36 * cin * cout, 16-B aligned), U = G g G^T (6x6) per (k, n) computed
  * in fp64 and rounded once, element (a, b) at xi = 6 b + a; flip as for smc_wino_weights_f32. */
 int smc_wino4_weights_f32(const float* w, int cout, int cin, int flip, float* uw, void* stream);

@@ -86,12 +86,14 @@ _SIGS = {
     "smc_conv3x3_wino_last_nsplit": (c_int, []),
     "smc_conv3x3_wino_route_count": (c_int, []),
     "smc_conv3x3_wino_route_name": (c_char_p, [c_int]),
+    "smc_conv3x3_wino_plan": (c_int, [c_int] * 6 + [P, c_int64, P, P, P]),
     "smc_wino_weights_f32": (c_int, [P, c_int, c_int, c_int, P, P]),
     "smc_conv3x3_wino4_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "smc_conv3x3_wino4_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P]),
     "smc_conv3x3_wino4_last_route": (c_int, []),
     "smc_conv3x3_wino4_route_count": (c_int, []),
     "smc_conv3x3_wino4_route_name": (c_char_p, [c_int]),
+    "smc_conv3x3_wino4_plan": (c_int, [c_int] * 6 + [P, P]),
     "smc_wino4_weights_f32": (c_int, [P, c_int, c_int, c_int, P, P]),
     "smc_wino_sp_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "smc_wino_sp_workspace_size": (c_int64, [c_int, c_int, c_int, c_int, c_int]),

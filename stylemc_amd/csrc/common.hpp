@@ -94,6 +94,14 @@ inline EpiExt epi_ext(const smc_conv_epilogue* e) {
     return x;
 }
 
+// The epilogue a conv call runs: *epi, or for NULL a plain store (STORE, linear, gain 1, no clamp).
+inline smc_conv_epilogue epi_or_default(const smc_conv_epilogue* epi) {
+    smc_conv_epilogue e{};
+    e.mode = SMC_EPI_STORE; e.act = SMC_ACT_LINEAR; e.gain = 1.f; e.clamp = -1.f;
+    if (epi) e = *epi;
+    return e;
+}
+
 // Modes PRELU / PRELU_GRAD / AFFINE and the residual (all modes) for output element idx = (n, o, yy, xx)
 // of a [.][cout][y_h][y_w] tensor.  MODACT's own math stays in epi_y (scale_c folded into its d).
 __device__ __forceinline__ float epi_ext_apply(int mode, float v, int n, int o, int64_t idx, int yy, int xx, int cout,

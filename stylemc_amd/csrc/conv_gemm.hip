@@ -2242,9 +2242,7 @@ int conv_gemm_impl(const float* x, int n, int cin, int in_h, int in_w, float* y,
     p.cout = cout; p.y_h = y_h; p.y_w = y_w;
     fill_phases(p, phases, nphases);
     SMC_CHECK(pl.max_m < (1LL << 31), "smc_conv_gemm_f32: too many positions");
-    smc_conv_epilogue e{};
-    e.mode = SMC_EPI_STORE; e.act = SMC_ACT_LINEAR; e.gain = 1.f; e.clamp = -1.f;
-    if (epi) e = *epi;
+    const smc_conv_epilogue e = smc::epi_or_default(epi);
     p.mode = e.mode; p.d = e.d; p.noise = e.noise; p.noise_nstride = e.noise_nstride;
     p.noise_strength = e.noise_strength; p.bias = e.bias; p.act = e.act; p.alpha = e.alpha; p.gain = e.gain;
     p.clamp = e.clamp; p.u_save = e.u_save;

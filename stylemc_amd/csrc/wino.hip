@@ -24,10 +24,15 @@
 //   * per k-quad (4 channels: MFMA k = lane >> 4) every lane reads ITS tile's 4x4 patch of ITS channel from
 //     LDS, transforms it in registers (32 adds; x s[n, c] for the style-scaled forward) and that is its B
 //     fragment for all 16 xi -- V never goes through LDS.  A fragments: 8 ds_read_b128 (bank-conflict free).
+//
+// Host side (the end of this file): smc_conv3x3_wino_ws_f32 and smc_modconv_conv1_torgb_f32 are plan (plan_wino(), the
+// one place that decides anything), prepare, launch (the plan's row of a route table) and finish; the support,
+// workspace and plan queries return fields of the same plan.
 #include <algorithm>
 #include <type_traits>
 
 #include "common.hpp"
+#include "wino_host.hpp"
 
 namespace {
 
@@ -616,97 +621,6 @@ __global__ __launch_bounds__(256) void wino_weights_kernel(const float* w, int c
     }
 }
 
-// tile columns of a workgroup's block: 32 or 16 (the kernel's instantiations), dividing the tile grid.  32 at most
-// (2 tile rows at W >= 64): against 64 it measured 477 / 468 against 480 / 473 us at r = 1024 fwd / data grad and
-// 18.64-18.70 against 18.72-18.74 ms per step over three interleaved rounds (profiles/r03_wino_tc_ab.txt).
-int wino_tc(int h, int w) {
-    if (h < 2 || h % 2 || w % 4 || w < 32) return 0;
-    for (int tc = 32; tc >= 16; tc /= 2)
-        if ((w / 2) % tc == 0 && (h / 2) % (WBT / tc) == 0) return tc;
-    return 0;
-}
-
-// One workgroup per work item.  (The persistent form -- PERSIST = 1, a resident grid looping over items with the
-// next item's first DMA under the current item's last step -- measured 3-18 % slower on every synthesis shape:
-// tools/probes/wino_ab.hip, profiles/r03_wino_ab.txt.)
-// (timing / counter probes only: tools/ builds a variant library with -DSMC_WINO_PROBE=n, see wino_kernel's PROBE)
-#ifndef SMC_WINO_PROBE
-#define SMC_WINO_PROBE 0
-#endif
-// Route report (smc_conv3x3_wino_last_route): one value per kernel instantiation smc_conv3x3_wino_ws_f32 can name,
-// the kernel template and its parameters as written in the launch being the identity.  The names are the stable
-// identity of a route; the numbers are an index into them for one build.  A record only: no launch decision reads it.
-#define SMC_WINO_ROUTES_SM(X, TC, SM) \
-    X("wino_kernel<" #TC "," #SM ",0>") X("wino_kernel<" #TC "," #SM ",1>") \
-    X("wino_kernel<" #TC "," #SM ",2>") X("wino_kernel<" #TC "," #SM ",3>")
-#define SMC_WINO_ROUTES_TC(X, TC) SMC_WINO_ROUTES_SM(X, TC, 1) SMC_WINO_ROUTES_SM(X, TC, 2)
-#define SMC_WINO_ROUTE_NAME(name) name,
-constexpr const char* kWinoRouteNames[] = {
-    "none",
-    SMC_WINO_ROUTES_TC(SMC_WINO_ROUTE_NAME, 32)
-    SMC_WINO_ROUTES_TC(SMC_WINO_ROUTE_NAME, 16)
-    "wino_x3r_kernel<1>", "wino_x3r_kernel<2>",
-};
-#undef SMC_WINO_ROUTE_NAME
-constexpr int kWinoRouteCount = sizeof(kWinoRouteNames) / sizeof(kWinoRouteNames[0]);
-// wino_kernel<TC, SM, EK>: the 8 forms of TC = 32, then those of 16, SM-major
-constexpr int wino_route(int tc, int sm, int ek) { return 1 + ((tc == 32 ? 0 : 1) * 2 + (sm - 1)) * 4 + ek; }
-constexpr int kWinoRouteX3R = 17;   // + EK - 1
-static_assert(wino_route(16, 2, 3) == kWinoRouteX3R - 1 && kWinoRouteCount == kWinoRouteX3R + 2,
-              "the route list and the numbering agree");
-
-thread_local int g_wino_route = 0;
-thread_local int g_wino_flags = 0;   // SMC_ROUTE_SPLIT_K | SMC_ROUTE_WINO_FOLD of that launch
-thread_local int g_wino_nsplit = 0;  // its K splits (1: one pass)
-
-template <int TC, int SM, int EK>
-void launch_wino(const WinoParams& p, int64_t items, hipStream_t st) {
-    g_wino_route = wino_route(TC, SM, EK);
-    hipLaunchKernelGGL((wino_kernel<TC, SM, EK, 0, SMC_WINO_PROBE>), dim3((unsigned)items, (unsigned)p.nsplit), dim3(256),
-                       0, st, p);
-}
-
-template <int SM, int EK>
-void launch_wino_tc(int tc, const WinoParams& p, int64_t items, hipStream_t st) {
-    if (tc == 32) launch_wino<32, SM, EK>(p, items, st);
-    else launch_wino<16, SM, EK>(p, items, st);
-}
-
-template <int EK>
-void launch_wino_s(bool has_s, int tc, const WinoParams& p, int64_t items, hipStream_t st) {
-    if (has_s) launch_wino_tc<1, EK>(tc, p, items, st);
-    else launch_wino_tc<2, EK>(tc, p, items, st);
-}
-
-// K splits of a launch: a grid of fewer than two workgroups per CU (the kernel's occupancy) leaves each SIMD one
-// wave to hide the DMA and LDS latency with -- the 32 x 32 synthesis conv of cin 512 (256 items, 64 K steps) ran at
-// a quarter of the MFMA rate.  Split K (a power of two dividing the step count, >= 8 steps per split) until the grid
-// holds kWinoSplitTarget workgroups; the partial tiles are summed by the modconv epilogue kernel.
-#ifndef SMC_WINO_SPLIT_TARGET
-#define SMC_WINO_SPLIT_TARGET 512
-#endif
-constexpr int64_t kWinoSplitTarget = SMC_WINO_SPLIT_TARGET;
-
-int wino_nsplit(int n, int cin, int cout, int h, int w) {
-    const int tc = wino_tc(h, w);
-    if (!tc) return 1;
-    const int64_t items = (int64_t)smc::plan_batch(n) * ((w / 2) / tc) * ((h / 2) / (WBT / tc)) * (cout / WBO);
-    const int nsteps = cin / WBK;
-    int ns = 1;
-    while (items * ns < kWinoSplitTarget && nsteps % (2 * ns) == 0 && nsteps / (2 * ns) >= 8) ns *= 2;
-    return ns;
-}
-
-// The fold applies where the per-image U is small (the 32 / 64-channel layers: 64 / 256 KB per image).
-constexpr int64_t kWinoFoldMaxCinCout = 128 * 128;
-int64_t wino_fold_bytes(int n, int cin, int cout) {
-    return (int64_t)cin * cout <= kWinoFoldMaxCinCout ? (int64_t)n * cin * 16 * cout * 4 : 0;
-}
-int64_t wino_split_bytes(int n, int cin, int cout, int h, int w) {
-    const int ns = wino_nsplit(n, cin, cout, h, w);
-    return ns > 1 ? (((int64_t)ns * n * cout * h * w * 4 + 255) / 256) * 256 : 0;
-}
-
 // ---------------------------------------------------------------------------------------------------
 // Split-bf16 F(2x2) for the 32-channel layer (cin = cout = 32: the r = 1024 conv1 forward and its data gradient).
 // The fp32 kernel above spends most of that launch in the fp32 MFMA K loop (219 us of 505 at r = 1024, batch 4:
@@ -1052,19 +966,181 @@ __global__ __launch_bounds__(512, 1) void wino_x3r_kernel(WinoParams p, const sh
     }
 }
 
-// bytes of split U planes the x3 path takes from the workspace (0: the shape runs the fp32 kernel)
-int64_t wino_x3_bytes(int n, int cin, int cout, int h, int w) {
-    return g_wino_x3 && cin == X3C && cout == X3C && wino_tc(h, w) == 32 ? (int64_t)n * X3_UBYTES : 0;
+// ---------------------------------------------------------------------------------------------------
+// Host side.  Every entry point runs four steps: plan (plan_wino: all decisions, from the call's arguments alone),
+// prepare (the kernel's operands; the workspace passes a plan asks for), launch (the plan's row of the route table),
+// finish (the split-K reduction).  The queries -- supported, workspace size, plan -- read the same plan.
+
+// K splits of a launch: a grid of fewer than two workgroups per CU (the kernel's occupancy) leaves each SIMD one
+// wave to hide the DMA and LDS latency with -- the 32 x 32 synthesis conv of cin 512 (256 items, 64 K steps) ran at
+// a quarter of the MFMA rate.  Split K (a power of two dividing the step count, >= 8 steps per split) until the grid
+// holds kWinoSplitTarget workgroups; the partial tiles are summed by the modconv epilogue kernel.
+#ifndef SMC_WINO_SPLIT_TARGET
+#define SMC_WINO_SPLIT_TARGET 512
+#endif
+constexpr int64_t kWinoSplitTarget = SMC_WINO_SPLIT_TARGET;
+// The fold applies where the per-image U is small (the 32 / 64-channel layers: 64 / 256 KB per image).
+constexpr int64_t kWinoFoldMaxCinCout = 128 * 128;
+
+// tile columns of a workgroup's block: 32 or 16 (the kernel's instantiations), dividing the tile grid.  32 at most
+// (2 tile rows at W >= 64): against 64 it measured 477 / 468 against 480 / 473 us at r = 1024 fwd / data grad and
+// 18.64-18.70 against 18.72-18.74 ms per step over three interleaved rounds (profiles/r03_wino_tc_ab.txt).
+int wino_tc(int h, int w) {
+    if (h < 2 || h % 2 || w % 4 || w < 32) return 0;
+    for (int tc = 32; tc >= 16; tc /= 2)
+        if ((w / 2) % tc == 0 && (h / 2) % (WBT / tc) == 0) return tc;
+    return 0;
 }
 
+struct WinoPlan {
+    int route;        // the row of kWinoRoutes (fused: kWinoRgbRoutes) that takes the call; 0: no kernel does
+    int tc;           // tile columns of a block
+    int gx, gy, ntn;  // blocks per image along x / y, output-channel blocks
+    int64_t items;    // work items = workgroups of one K split
+    int sm, ek;       // the kernel's style and epilogue forms
+    int nsplit;       // K splits of the launch (1: one pass)
+    bool fold;        // the style goes into per-image U in the workspace first (the launch then runs SM 2)
+    bool x3;          // the split-bf16 kernel takes the call
+    int64_t split_bytes, fold_bytes, x3_bytes;  // what the shape can use of a workspace: [split partials][folded U],
+    int64_t fold_off;                           // the folded U behind the partials; or the split-bf16 planes alone
+    int64_t need;     // the workspace the queries ask for; a smaller one is not used at all
+    int flags;        // SMC_ROUTE_SPLIT_K | SMC_ROUTE_WINO_FOLD
+};
+
+// ---- launch: one launcher per kernel template, instantiated by the rows of the route tables
+// One workgroup per work item.  (The persistent form -- PERSIST = 1, a resident grid looping over items with the
+// next item's first DMA under the current item's last step -- measured 3-18 % slower on every synthesis shape:
+// tools/probes/wino_ab.hip, profiles/r03_wino_ab.txt.)
+// (timing / counter probes only: tools/ builds a variant library with -DSMC_WINO_PROBE=n, see wino_kernel's PROBE)
+#ifndef SMC_WINO_PROBE
+#define SMC_WINO_PROBE 0
+#endif
+template <int TC, int SM, int EK>
+void run_wino_kernel(const WinoPlan& pl, const WinoParams& p, const short*, int64_t, hipStream_t st) {
+    hipLaunchKernelGGL((wino_kernel<TC, SM, EK, 0, SMC_WINO_PROBE>), dim3((unsigned)pl.items, (unsigned)pl.nsplit),
+                       dim3(256), 0, st, p);
+}
+
+// planes: the split U planes of wino_x3_pack_kernel, plane_nstride bf16 between two images' (0: one set)
 template <int EK>
-void launch_wino_x3(const WinoParams& p, const short* planes, int64_t nstride, hipStream_t st) {
+void run_wino_x3r_kernel(const WinoPlan&, const WinoParams& p, const short* planes, int64_t plane_nstride,
+                         hipStream_t st) {
     WinoParams q = p;   // items of one tile row (32 tiles)
     q.gy = p.h / 2;
     const int per = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)q.gx * q.gy, smc::device_cu_count() / p.n));
-    g_wino_route = kWinoRouteX3R + EK - 1;
-    hipLaunchKernelGGL(wino_x3r_kernel<EK>, dim3((unsigned)per, (unsigned)p.n), dim3(512), 0, st, q, planes, nstride);
+    hipLaunchKernelGGL(wino_x3r_kernel<EK>, dim3((unsigned)per, (unsigned)p.n), dim3(512), 0, st, q, planes,
+                       plane_nstride);
 }
+
+template <int TC, int SM>
+void run_wino_rgb_kernel(const WinoPlan& pl, const WinoParams& p, const WinoRgb& rg, hipStream_t st) {
+    hipLaunchKernelGGL((wino_rgb_kernel<TC, SM>), dim3((unsigned)pl.items), dim3(256), 0, st, p, rg);
+}
+
+// Route lists (smc::RouteRow).  wino_kernel<TC,SM,EK>: the eight forms of TC 32, then those of TC 16.
+enum { K_wino_kernel, K_wino_x3r_kernel, K_wino_rgb_kernel };
+#define SMC_WINO_ROUTES(X) \
+    SMC_WINO_ROUTES_SM(X, 32,1) SMC_WINO_ROUTES_SM(X, 32,2) SMC_WINO_ROUTES_SM(X, 16,1) SMC_WINO_ROUTES_SM(X, 16,2) \
+    X(wino_x3r_kernel, 1) X(wino_x3r_kernel, 2)
+#define SMC_WINO_ROUTES_SM(X, TC, SM) \
+    X(wino_kernel, TC,SM,0) X(wino_kernel, TC,SM,1) X(wino_kernel, TC,SM,2) X(wino_kernel, TC,SM,3)
+#define SMC_WINO_RGB_ROUTES(X) \
+    X(wino_rgb_kernel, 32,1) X(wino_rgb_kernel, 32,2) X(wino_rgb_kernel, 16,1) X(wino_rgb_kernel, 16,2)
+
+using WinoRun = void (*)(const WinoPlan&, const WinoParams&, const short*, int64_t, hipStream_t);
+using WinoRgbRun = void (*)(const WinoPlan&, const WinoParams&, const WinoRgb&, hipStream_t);
+constexpr smc::RouteRow<WinoRun> kWinoRoutes[] = {{"none", nullptr, -1, {}}, SMC_WINO_ROUTES(SMC_WINO_ROUTE_ROW)};
+constexpr smc::RouteRow<WinoRgbRun> kWinoRgbRoutes[] = {{"none", nullptr, -1, {}},
+                                                        SMC_WINO_RGB_ROUTES(SMC_WINO_ROUTE_ROW)};
+constexpr int kWinoRouteCount = sizeof(kWinoRoutes) / sizeof(kWinoRoutes[0]);
+constexpr int kWinoRgbRouteCount = sizeof(kWinoRgbRoutes) / sizeof(kWinoRgbRoutes[0]);
+
+// ---- plan: everything the entry points decide, from the call's arguments alone (no launch, no write).
+// has_s: the call passes a style scale; epi: its epilogue or NULL; ws_bytes: the workspace it offers (0: none);
+// fused: the conv1 + ToRGB form (wino_rgb_kernel), which takes only what one pass of the fp32 kernel computes.
+WinoPlan plan_wino(int n, int cin, int cout, int h, int w, bool has_s, const smc_conv_epilogue* epi, int64_t ws_bytes,
+                   bool fused) {
+    WinoPlan pl{};
+    if (n < 1 || cin < WBK || cin % WBK || cout < WBO || cout % WBO) return pl;
+    if ((int64_t)n * cin * h * w * 4 >= (1LL << 31)) return pl;  // raw buffer offsets are 32-bit
+    pl.tc = wino_tc(h, w);
+    if (!pl.tc) return pl;
+    pl.gx = (w / 2) / pl.tc;
+    pl.gy = (h / 2) / (WBT / pl.tc);
+    pl.ntn = cout / WBO;
+    const int64_t per_image = (int64_t)pl.gx * pl.gy * pl.ntn;
+    pl.items = n * per_image;
+    // the split count is planned for the planning batch; the partial planes hold the call's own n images
+    const int nsteps = cin / WBK;
+    int ns = 1;
+    while (smc::plan_batch(n) * per_image * ns < kWinoSplitTarget && nsteps % (2 * ns) == 0 && nsteps / (2 * ns) >= 8)
+        ns *= 2;
+    pl.split_bytes = ns > 1 ? (((int64_t)ns * n * cout * h * w * 4 + 255) / 256) * 256 : 0;
+    pl.fold_bytes = SMC_WINO_FOLD && (int64_t)cin * cout <= kWinoFoldMaxCinCout ? (int64_t)n * cin * 16 * cout * 4 : 0;
+    pl.x3_bytes = g_wino_x3 && cin == X3C && cout == X3C && pl.tc == 32 ? (int64_t)n * X3_UBYTES : 0;
+    pl.fold_off = pl.split_bytes;
+    pl.need = std::max(pl.split_bytes + pl.fold_bytes, pl.x3_bytes);
+    const smc_conv_epilogue e = smc::epi_or_default(epi);
+    pl.ek = smc::epi_body(e);
+    pl.nsplit = 1;
+    if (fused) {
+        // one pass of wino_kernel's EK 1 without u_save (a NULL epilogue asks about the shape alone); where the
+        // two-launch path would split K or run the split-bf16 kernel, it keeps the call
+        if (cout != WBO || pl.split_bytes > 0 || pl.x3_bytes > 0 || (epi && (pl.ek != 1 || e.u_save))) return pl;
+        pl.ek = 1;
+    }
+    // a workspace smaller than the queries ask for is not used: neither a fold nor a split
+    const bool ws_ok = pl.need > 0 && ws_bytes >= pl.need;
+    const bool noise_ok = !e.noise || ((reinterpret_cast<uintptr_t>(e.noise) & 15) == 0 && e.noise_nstride % 4 == 0);
+    pl.x3 = pl.x3_bytes > 0 && ws_ok && noise_ok && (pl.ek == 1 || (pl.ek == 2 && g_wino_x3 >= 2));
+    if (pl.x3) {   // (else the fp32 kernel, as with the mode off)
+        pl.route = smc::route_of(kWinoRoutes, K_wino_x3r_kernel, pl.ek);
+        return pl;
+    }
+    pl.fold = has_s && pl.fold_bytes > 0 && ws_ok;
+    pl.sm = has_s && !pl.fold ? 1 : 2;
+    if (pl.fold) pl.flags |= SMC_ROUTE_WINO_FOLD;
+    if (pl.split_bytes > 0 && ws_ok) {   // raw partial tiles (EK 3); smc_modconv_epilogue_f32 runs the epilogue
+        pl.nsplit = ns;
+        pl.ek = 3;
+        pl.flags |= SMC_ROUTE_SPLIT_K;
+    }
+    pl.route = fused ? smc::route_of(kWinoRgbRoutes, K_wino_rgb_kernel, pl.tc, pl.sm)
+                     : smc::route_of(kWinoRoutes, K_wino_kernel, pl.tc, pl.sm, pl.ek);
+    return pl;
+}
+
+// ---- prepare
+WinoParams wino_params(const WinoPlan& pl, const float* x, int n, int cin, int h, int w, float* y, int cout,
+                       const float* uw, const float* s_in, const smc_conv_epilogue& e) {
+    WinoParams p{};
+    p.x = x; p.n = n; p.cin = cin; p.h = h; p.w = w; p.y = y; p.cout = cout; p.uw = uw; p.s = s_in;
+    smc::fill_epilogue(p, e);
+    p.gx = pl.gx; p.gy = pl.gy; p.ntn = pl.ntn;
+    p.nsplit = pl.nsplit;
+    return p;
+}
+
+// Per-image U with the style folded in, at uf (wino_ufold_kernel); the launch then reads it and no style.
+// (who: the entry point, as its messages name it)
+int launch_ufold(WinoParams& p, float* uf, hipStream_t st, const char* who, const char* who_fold) {
+    SMC_CHECK((reinterpret_cast<uintptr_t>(uf) & 15) == 0, "%s: workspace alignment", who);
+    const int per4 = p.cin * 4 * p.cout;   // float4 per image
+    const int64_t total4 = (int64_t)p.n * per4;
+    hipLaunchKernelGGL(wino_ufold_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(total4, 256), 4096)),
+                       dim3(256), 0, st, reinterpret_cast<const float4*>(p.uw), p.s, reinterpret_cast<float4*>(uf),
+                       p.cin, per4, total4);
+    const int rc = smc::check_launch(who_fold);
+    p.uw = uf;
+    p.u_nstride = (int64_t)p.cin * 16 * p.cout;
+    p.s = nullptr;
+    return rc;
+}
+
+thread_local int g_wino_route = 0;
+thread_local int g_wino_flags = 0;   // SMC_ROUTE_SPLIT_K | SMC_ROUTE_WINO_FOLD of that launch
+thread_local int g_wino_nsplit = 0;  // its K splits (1: one pass)
+thread_local int g_wino_rgb_route = 0;
 
 }  // namespace
 
@@ -1075,9 +1151,7 @@ SMC_API int smc_set_wino_x3(int mode) {
 }
 
 SMC_API int smc_conv3x3_wino_supported(int n, int cin, int cout, int h, int w) {
-    if (n < 1 || cin < WBK || cin % WBK || cout < WBO || cout % WBO) return 0;
-    if ((int64_t)n * cin * h * w * 4 >= (1LL << 31)) return 0;  // raw buffer offsets are 32-bit
-    return wino_tc(h, w) != 0;
+    return plan_wino(n, cin, cout, h, w, false, nullptr, 0, false).route != 0;
 }
 
 SMC_API int smc_wino_weights_f32(const float* w, int cout, int cin, int flip, float* uw, void* stream) {
@@ -1089,10 +1163,19 @@ SMC_API int smc_wino_weights_f32(const float* w, int cout, int cin, int flip, fl
     return smc::check_launch("smc_wino_weights_f32");
 }
 
-// [split-K partial planes (when the grid is too small)][per-image folded U (forward with a style scale)]
+// [split-K partial planes (when the grid is too small)][per-image folded U (forward with a style scale)], or the
+// split-bf16 planes where they are larger
 SMC_API int64_t smc_conv3x3_wino_workspace_size(int n, int cin, int cout, int h, int w) {
-    if (!smc_conv3x3_wino_supported(n, cin, cout, h, w)) return 0;
-    return std::max(wino_split_bytes(n, cin, cout, h, w) + wino_fold_bytes(n, cin, cout), wino_x3_bytes(n, cin, cout, h, w));
+    return plan_wino(n, cin, cout, h, w, false, nullptr, 0, false).need;
+}
+
+SMC_API int smc_conv3x3_wino_plan(int n, int cin, int cout, int h, int w, int has_style, const smc_conv_epilogue* epi,
+                                  int64_t workspace_bytes, int* route, int* flags, int* nsplit) {
+    const WinoPlan pl = plan_wino(n, cin, cout, h, w, has_style != 0, epi, workspace_bytes, false);
+    if (route) *route = pl.route;
+    if (flags) *flags = pl.flags;
+    if (nsplit) *nsplit = pl.route ? pl.nsplit : 0;
+    return pl.route ? SMC_OK : SMC_ERR_UNSUPPORTED;
 }
 
 SMC_API int smc_conv3x3_wino_f32(const float* x, int n, int cin, int h, int w, float* y, int cout, const float* uw,
@@ -1107,96 +1190,55 @@ SMC_API int smc_conv3x3_wino_ws_f32(const float* x, int n, int cin, int h, int w
     g_wino_flags = 0;
     g_wino_nsplit = 0;
     SMC_CHECK(x && y && uw, "smc_conv3x3_wino_f32: null pointer");
-    if (!smc_conv3x3_wino_supported(n, cin, cout, h, w)) {
+    // ---- plan
+    const WinoPlan pl = plan_wino(n, cin, cout, h, w, s_in != nullptr, epi, workspace ? workspace_bytes : 0, false);
+    if (!pl.route) {
         smc::set_error("smc_conv3x3_wino_f32: no Winograd kernel for n=%d cin=%d cout=%d %dx%d", n, cin, cout, h, w);
         return SMC_ERR_UNSUPPORTED;
     }
     SMC_CHECK((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0 &&
                   (reinterpret_cast<uintptr_t>(uw) & 15) == 0,
               "smc_conv3x3_wino_f32: x / uw must be 16-B and y 8-B aligned");
-    smc_conv_epilogue e{};
-    e.mode = SMC_EPI_STORE; e.act = SMC_ACT_LINEAR; e.gain = 1.f; e.clamp = -1.f;
-    if (epi) e = *epi;
-    SMC_CHECK(e.mode >= SMC_EPI_STORE && e.mode <= SMC_EPI_AFFINE, "smc_conv3x3_wino_f32: bad epilogue mode %d", e.mode);
-    SMC_CHECK((e.mode != SMC_EPI_PRELU && e.mode != SMC_EPI_PRELU_GRAD) || e.alpha_c,
-              "smc_conv3x3_wino_f32: PReLU epilogue needs alpha_c");
-    SMC_CHECK(e.mode != SMC_EPI_PRELU_GRAD || e.act_ref, "smc_conv3x3_wino_f32: PRELU_GRAD needs act_ref");
-    SMC_CHECK(!e.u_save || (reinterpret_cast<uintptr_t>(e.u_save) & 7) == 0, "smc_conv3x3_wino_f32: u_save alignment");
-    WinoParams p{};
-    p.x = x; p.n = n; p.cin = cin; p.h = h; p.w = w; p.y = y; p.cout = cout; p.uw = uw; p.s = s_in;
-    p.mode = e.mode; p.d = e.d; p.noise = e.noise; p.noise_nstride = e.noise_nstride;
-    p.noise_strength = e.noise_strength; p.bias = e.bias; p.act = e.act; p.alpha = e.alpha; p.gain = e.gain;
-    p.clamp = e.clamp; p.u_save = e.u_save;
-    p.ext = smc::epi_ext(epi);
-    const int tc = wino_tc(h, w);
-    p.gx = (w / 2) / tc;
-    p.gy = (h / 2) / (WBT / tc);
-    p.ntn = cout / WBO;
-    const int64_t items = (int64_t)n * p.gx * p.gy * p.ntn;
-    SMC_CHECK(items < (1LL << 31), "smc_conv3x3_wino_f32: grid too large");
+    const smc_conv_epilogue e = smc::epi_or_default(epi);
+    int rc = smc::check_epilogue(e, "smc_conv3x3_wino_f32", 8);
+    if (rc != SMC_OK) return rc;
+    SMC_CHECK(pl.items < (1LL << 31), "smc_conv3x3_wino_f32: grid too large");
+    // ---- prepare
+    WinoParams p = wino_params(pl, x, n, cin, h, w, y, cout, uw, s_in, e);
     hipStream_t st = smc::as_stream(stream);
-    // split K when the caller passed the workspace smc_conv3x3_wino_workspace_size() asks for (without one: one
-    // workgroup per item over the whole K range, as before)
-    const int64_t need = smc_conv3x3_wino_workspace_size(n, cin, cout, h, w);
-    const int64_t split_bytes = wino_split_bytes(n, cin, cout, h, w), fold_bytes = wino_fold_bytes(n, cin, cout);
-    const bool ws_ok = need > 0 && workspace && workspace_bytes >= need;
-    const bool modact_plain = p.mode == SMC_EPI_MODACT && !p.ext.residual;
-    const bool ek1 = modact_plain && p.act == SMC_ACT_LRELU && p.alpha >= 0.f && p.alpha <= 1.f && p.clamp >= 0.f;
-    const bool ek2 = modact_plain && p.act == SMC_ACT_LINEAR && p.clamp < 0.f;
-    const bool noise_ok = !e.noise || ((reinterpret_cast<uintptr_t>(e.noise) & 15) == 0 && e.noise_nstride % 4 == 0);
-    if (wino_x3_bytes(n, cin, cout, h, w) > 0 && ws_ok && noise_ok && (ek1 || (ek2 && g_wino_x3 >= 2))) {
+    const short* planes = nullptr;
+    int64_t plane_nstride = 0;
+    if (pl.x3) {
         // the 32-channel layer on the bf16 matrix core: split U planes (x s[n, c] when scaled) into the workspace
         SMC_CHECK((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "smc_conv3x3_wino_ws_f32: workspace alignment");
-        short* planes = reinterpret_cast<short*>(workspace);
         const int64_t total = (int64_t)(s_in ? n : 1) * (X3_UPLANE / 3);
         hipLaunchKernelGGL(wino_x3_pack_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(total, 256), 4096)),
-                           dim3(256), 0, st, uw, s_in, planes, total);
-        const int rc = smc::check_launch("smc_conv3x3_wino_ws_f32 (x3 planes)");
+                           dim3(256), 0, st, uw, s_in, reinterpret_cast<short*>(workspace), total);
+        rc = smc::check_launch("smc_conv3x3_wino_ws_f32 (x3 planes)");
         if (rc != SMC_OK) return rc;
-        const int64_t ns = s_in ? X3_UPLANE : 0;
-        g_wino_nsplit = 1;
-        if (ek1) launch_wino_x3<1>(p, planes, ns, st);
-        else launch_wino_x3<2>(p, planes, ns, st);
-        return smc::check_launch("smc_conv3x3_wino_ws_f32 (x3)");
+        planes = reinterpret_cast<const short*>(workspace);
+        plane_nstride = s_in ? X3_UPLANE : 0;
     }
-    if (SMC_WINO_FOLD && s_in && fold_bytes > 0 && ws_ok) {
-        float* uf = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + split_bytes);
-        SMC_CHECK((reinterpret_cast<uintptr_t>(uf) & 15) == 0, "smc_conv3x3_wino_ws_f32: workspace alignment");
-        const int per4 = cin * 4 * cout;   // float4 per image
-        const int64_t total4 = (int64_t)n * per4;
-        hipLaunchKernelGGL(wino_ufold_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(total4, 256), 4096)),
-                           dim3(256), 0, st, reinterpret_cast<const float4*>(uw), s_in, reinterpret_cast<float4*>(uf),
-                           cin, per4, total4);
-        const int rc = smc::check_launch("smc_conv3x3_wino_ws_f32 (style fold)");
+    if (pl.fold) {
+        rc = launch_ufold(p, reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + pl.fold_off), st,
+                          "smc_conv3x3_wino_ws_f32", "smc_conv3x3_wino_ws_f32 (style fold)");
         if (rc != SMC_OK) return rc;
-        p.uw = uf;
-        p.u_nstride = (int64_t)cin * 16 * cout;
-        p.s = nullptr;
-        s_in = nullptr;
-        g_wino_flags |= SMC_ROUTE_WINO_FOLD;
     }
-    p.nsplit = 1;
-    g_wino_nsplit = 1;
-    if (split_bytes > 0 && ws_ok) {
+    if (pl.nsplit > 1) {
         SMC_CHECK((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "smc_conv3x3_wino_ws_f32: workspace alignment");
-        p.nsplit = wino_nsplit(n, cin, cout, h, w);
-        g_wino_nsplit = p.nsplit;
-        g_wino_flags |= SMC_ROUTE_SPLIT_K;
         p.split_stride = (int64_t)n * cout * h * w;
         p.ws = workspace;
-        launch_wino_s<3>(s_in != nullptr, tc, p, items, st);
-        const int rc = smc::check_launch("smc_conv3x3_wino_ws_f32");
-        if (rc != SMC_OK) return rc;
-        return smc_modconv_epilogue_f32(workspace, p.nsplit, p.split_stride, y, n, cout, h, w, &e, stream);
     }
-    // the synthesis' two MODACT forms get an epilogue body with the activation fixed at compile time
-    if (ek1)
-        launch_wino_s<1>(s_in != nullptr, tc, p, items, st);
-    else if (ek2)
-        launch_wino_s<2>(s_in != nullptr, tc, p, items, st);
-    else
-        launch_wino_s<0>(s_in != nullptr, tc, p, items, st);
-    return smc::check_launch("smc_conv3x3_wino_f32");
+    // ---- launch
+    g_wino_route = pl.route;
+    g_wino_flags = pl.flags;
+    g_wino_nsplit = pl.nsplit;
+    kWinoRoutes[pl.route].run(pl, p, planes, plane_nstride, st);
+    rc = smc::check_launch(pl.x3 ? "smc_conv3x3_wino_ws_f32 (x3)"
+                                 : pl.nsplit > 1 ? "smc_conv3x3_wino_ws_f32" : "smc_conv3x3_wino_f32");
+    // ---- finish: the sum of the K splits and the call's epilogue
+    if (rc != SMC_OK || pl.nsplit == 1) return rc;
+    return smc_modconv_epilogue_f32(workspace, pl.nsplit, p.split_stride, y, n, cout, h, w, &e, stream);
 }
 
 SMC_API int smc_conv3x3_wino_last_route(void) { return g_wino_route; }
@@ -1207,51 +1249,22 @@ SMC_API int smc_conv3x3_wino_last_nsplit(void) { return g_wino_nsplit; }
 
 SMC_API int smc_conv3x3_wino_route_count(void) { return kWinoRouteCount; }
 
-SMC_API const char* smc_conv3x3_wino_route_name(int route) {
-    return route >= 0 && route < kWinoRouteCount ? kWinoRouteNames[route] : nullptr;
-}
+SMC_API const char* smc_conv3x3_wino_route_name(int route) { return smc::route_name(kWinoRoutes, route); }
 
 // ---------------------------------------------------------------------------------------------------
 // conv1 + ToRGB of a 32-channel synthesis block in one launch (wino_rgb_kernel): the block's last conv and the 1x1
-// ToRGB that reads its output, with y stored only where the caller needs it.  A route report of its own.
-namespace {
-
-constexpr const char* kWinoRgbRouteNames[] = {
-    "none", "wino_rgb_kernel<32,1>", "wino_rgb_kernel<32,2>", "wino_rgb_kernel<16,1>", "wino_rgb_kernel<16,2>",
-};
-constexpr int kWinoRgbRouteCount = sizeof(kWinoRgbRouteNames) / sizeof(kWinoRgbRouteNames[0]);
-constexpr int wino_rgb_route(int tc, int sm) { return 1 + (tc == 32 ? 0 : 2) + (sm - 1); }
-thread_local int g_wino_rgb_route = 0;
-
-template <int TC, int SM>
-void launch_wino_rgb(const WinoParams& p, const WinoRgb& rg, int64_t items, hipStream_t st) {
-    g_wino_rgb_route = wino_rgb_route(TC, SM);
-    hipLaunchKernelGGL((wino_rgb_kernel<TC, SM>), dim3((unsigned)items), dim3(256), 0, st, p, rg);
-}
-
-// the epilogue the fused kernel computes: conv1's MODACT lrelu + gain + clamp (wino_kernel's EK 1), no u_save
-bool wino_rgb_epi_ok(const smc_conv_epilogue* e) {
-    if (!e) return true;
-    const smc::EpiExt ext = smc::epi_ext(e);
-    return e->mode == SMC_EPI_MODACT && !ext.residual && e->act == SMC_ACT_LRELU && e->alpha >= 0.f && e->alpha <= 1.f &&
-           e->clamp >= 0.f && !e->u_save;
-}
-
-}  // namespace
-
+// ToRGB that reads its output, with y stored only where the caller needs it.  The fused form of the same plan, with a
+// route report of its own.
 SMC_API int smc_modconv_conv1_torgb_supported(int n, int cin, int cout, int h, int w, int cout_rgb,
                                               const smc_conv_epilogue* epi) {
-    if (cout != WBO || cout_rgb < 1 || cout_rgb > WRGB) return 0;
-    if (!smc_conv3x3_wino_supported(n, cin, cout, h, w)) return 0;
-    // one pass: where the two-launch path plans split-K (or the experimental split-bf16 kernel is on) it keeps the call
-    if (wino_nsplit(n, cin, cout, h, w) != 1 || wino_x3_bytes(n, cin, cout, h, w) > 0) return 0;
-    return wino_rgb_epi_ok(epi) ? 1 : 0;
+    if (cout_rgb < 1 || cout_rgb > WRGB) return 0;
+    return plan_wino(n, cin, cout, h, w, false, epi, 0, true).route != 0;
 }
 
 // [per-image folded U]: with it the launch runs the folded form (SM 2), without it the style scale in the kernel (SM 1)
 SMC_API int64_t smc_modconv_conv1_torgb_workspace_size(int n, int cin, int cout, int h, int w) {
-    if (!smc_modconv_conv1_torgb_supported(n, cin, cout, h, w, 1, nullptr)) return 0;
-    return SMC_WINO_FOLD ? wino_fold_bytes(n, cin, cout) : 0;
+    const WinoPlan pl = plan_wino(n, cin, cout, h, w, false, nullptr, 0, true);
+    return pl.route ? pl.need : 0;
 }
 
 SMC_API int smc_modconv_conv1_torgb_f32(const float* x, int n, int cin, int h, int w, float* y, int cout,
@@ -1262,9 +1275,11 @@ SMC_API int smc_modconv_conv1_torgb_f32(const float* x, int n, int cin, int h, i
     g_wino_rgb_route = 0;
     SMC_CHECK(x && uw, "smc_modconv_conv1_torgb_f32: null pointer (x, uw)");
     SMC_CHECK(rgb && w_rgb && s_rgb, "smc_modconv_conv1_torgb_f32: null pointer (rgb, w_rgb, s_rgb)");
+    // ---- plan
     // (a NULL epi is the STORE default of smc_conv3x3_wino_ws_f32: no fused form; the predicate takes NULL to ask about
     // the shape alone)
-    if (!epi || !smc_modconv_conv1_torgb_supported(n, cin, cout, h, w, cout_rgb, epi)) {
+    const WinoPlan pl = plan_wino(n, cin, cout, h, w, s_in != nullptr, epi, workspace ? workspace_bytes : 0, true);
+    if (!epi || !pl.route || cout_rgb < 1 || cout_rgb > WRGB) {
         smc::set_error("smc_modconv_conv1_torgb_f32: no fused kernel for n=%d cin=%d cout=%d %dx%d cout_rgb=%d with "
                        "this epilogue", n, cin, cout, h, w, cout_rgb);
         return SMC_ERR_UNSUPPORTED;
@@ -1272,42 +1287,21 @@ SMC_API int smc_modconv_conv1_torgb_f32(const float* x, int n, int cin, int h, i
     SMC_CHECK((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0 &&
                   (reinterpret_cast<uintptr_t>(uw) & 15) == 0 && (reinterpret_cast<uintptr_t>(rgb) & 3) == 0,
               "smc_modconv_conv1_torgb_f32: x / uw must be 16-B, y 8-B and rgb 4-B aligned");
-    WinoParams p{};
-    p.x = x; p.n = n; p.cin = cin; p.h = h; p.w = w; p.y = y; p.cout = cout; p.uw = uw; p.s = s_in;
-    p.mode = epi->mode; p.d = epi->d; p.noise = epi->noise; p.noise_nstride = epi->noise_nstride;
-    p.noise_strength = epi->noise_strength; p.bias = epi->bias; p.act = epi->act; p.alpha = epi->alpha;
-    p.gain = epi->gain; p.clamp = epi->clamp;
-    p.ext = smc::epi_ext(epi);
-    const int tc = wino_tc(h, w);
-    p.gx = (w / 2) / tc;
-    p.gy = (h / 2) / (WBT / tc);
-    p.ntn = 1;
-    p.nsplit = 1;
-    const int64_t items = (int64_t)n * p.gx * p.gy;
-    SMC_CHECK(items < (1LL << 31), "smc_modconv_conv1_torgb_f32: grid too large");
-    WinoRgb rg{w_rgb, s_rgb, b_rgb, clamp_rgb, cout_rgb, rgb};
+    int rc = smc::check_epilogue(*epi, "smc_modconv_conv1_torgb_f32", 8);
+    if (rc != SMC_OK) return rc;
+    SMC_CHECK(pl.items < (1LL << 31), "smc_modconv_conv1_torgb_f32: grid too large");
+    // ---- prepare
+    WinoParams p = wino_params(pl, x, n, cin, h, w, y, cout, uw, s_in, *epi);
+    const WinoRgb rg{w_rgb, s_rgb, b_rgb, clamp_rgb, cout_rgb, rgb};
     hipStream_t st = smc::as_stream(stream);
-    const int64_t fold_bytes = smc_modconv_conv1_torgb_workspace_size(n, cin, cout, h, w);
-    if (s_in && fold_bytes > 0 && workspace && workspace_bytes >= fold_bytes) {
-        SMC_CHECK((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "smc_modconv_conv1_torgb_f32: workspace alignment");
-        const int per4 = cin * 4 * cout;   // float4 per image
-        const int64_t total4 = (int64_t)n * per4;
-        hipLaunchKernelGGL(wino_ufold_kernel, dim3((unsigned)std::min<int64_t>(smc::ceil_div(total4, 256), 4096)),
-                           dim3(256), 0, st, reinterpret_cast<const float4*>(uw), s_in,
-                           reinterpret_cast<float4*>(workspace), cin, per4, total4);
-        const int rc = smc::check_launch("smc_modconv_conv1_torgb_f32 (style fold)");
+    if (pl.fold) {
+        rc = launch_ufold(p, reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + pl.fold_off), st,
+                          "smc_modconv_conv1_torgb_f32", "smc_modconv_conv1_torgb_f32 (style fold)");
         if (rc != SMC_OK) return rc;
-        p.uw = workspace;
-        p.u_nstride = (int64_t)cin * 16 * cout;
-        p.s = nullptr;
     }
-    if (p.s) {
-        if (tc == 32) launch_wino_rgb<32, 1>(p, rg, items, st);
-        else launch_wino_rgb<16, 1>(p, rg, items, st);
-    } else {
-        if (tc == 32) launch_wino_rgb<32, 2>(p, rg, items, st);
-        else launch_wino_rgb<16, 2>(p, rg, items, st);
-    }
+    // ---- launch (one pass: nothing to finish)
+    g_wino_rgb_route = pl.route;
+    kWinoRgbRoutes[pl.route].run(pl, p, rg, st);
     return smc::check_launch("smc_modconv_conv1_torgb_f32");
 }
 
@@ -1315,6 +1309,4 @@ SMC_API int smc_modconv_conv1_torgb_last_route(void) { return g_wino_rgb_route; 
 
 SMC_API int smc_modconv_conv1_torgb_route_count(void) { return kWinoRgbRouteCount; }
 
-SMC_API const char* smc_modconv_conv1_torgb_route_name(int route) {
-    return route >= 0 && route < kWinoRgbRouteCount ? kWinoRgbRouteNames[route] : nullptr;
-}
+SMC_API const char* smc_modconv_conv1_torgb_route_name(int route) { return smc::route_name(kWinoRgbRoutes, route); }

@@ -22,10 +22,14 @@
 //     [4][9][64][4] one step ahead, the raw input rows of the block's 10 x 72 patch two steps ahead (16-B chunks from
 //     column 4 tx0 - 4; the buffer range check zero-fills the image border).  LDS: 2 x (U + patch + V) = 132 KiB;
 //     one barrier per step.
+//
+// Host side (the end of this file): smc_conv3x3_wino4_f32 is plan (plan_wino4()), prepare and launch (the plan's row
+// of the route table), as wino.hip.
 #include <algorithm>
 #include <type_traits>
 
 #include "common.hpp"
+#include "wino_host.hpp"
 
 namespace {
 
@@ -428,41 +432,59 @@ __global__ __launch_bounds__(256) void wino4_weights_kernel(const float* w, int 
     }
 }
 
-// Route report (smc_conv3x3_wino4_last_route): one value per wino4_kernel<SM, EK> instantiation.  A record only: no
-// launch decision reads it.
-constexpr const char* kW4RouteNames[] = {
-    "none",
-    "wino4_kernel<1,0>", "wino4_kernel<1,1>", "wino4_kernel<1,2>",
-    "wino4_kernel<2,0>", "wino4_kernel<2,1>", "wino4_kernel<2,2>",
+// ---------------------------------------------------------------------------------------------------
+// Host side: plan, prepare, launch, as wino.hip (one pass, no workspace: nothing to finish).
+struct W4Plan {
+    int route;        // the row of kW4Routes that takes the call; 0: no kernel does
+    int gx, gy, ntn;  // tile blocks per image along x / y, output-channel blocks
+    int64_t items;    // work item = 64 output channels x 32 tiles (2 tile rows x 16 tile columns = 8 x 64 outputs)
+    int sm, ek;       // the kernel's style and epilogue forms
 };
-constexpr int kW4RouteCount = sizeof(kW4RouteNames) / sizeof(kW4RouteNames[0]);
-thread_local int g_w4_route = 0;
 
 template <int SM, int EK>
-void launch_w4(const Wino4Params& p, int64_t items, hipStream_t st) {
-    static_assert(1 + (SM - 1) * 3 + EK < kW4RouteCount, "the route list and the numbering agree");
-    g_w4_route = 1 + (SM - 1) * 3 + EK;
-    hipLaunchKernelGGL((wino4_kernel<SM, EK>), dim3((unsigned)items), dim3(W4_THREADS), 0, st, p);
+void run_wino4_kernel(const W4Plan& pl, const Wino4Params& p, hipStream_t st) {
+    hipLaunchKernelGGL((wino4_kernel<SM, EK>), dim3((unsigned)pl.items), dim3(W4_THREADS), 0, st, p);
 }
 
-template <int EK>
-void launch_w4_s(bool has_s, const Wino4Params& p, int64_t items, hipStream_t st) {
-    if (has_s) launch_w4<1, EK>(p, items, st);
-    else launch_w4<2, EK>(p, items, st);
+// Route list (smc::RouteRow): wino4_kernel<SM,EK>
+enum { K_wino4_kernel };
+#define SMC_WINO4_ROUTES(X)                                                   \
+    X(wino4_kernel, 1,0) X(wino4_kernel, 1,1) X(wino4_kernel, 1,2)            \
+    X(wino4_kernel, 2,0) X(wino4_kernel, 2,1) X(wino4_kernel, 2,2)
+using W4Run = void (*)(const W4Plan&, const Wino4Params&, hipStream_t);
+constexpr smc::RouteRow<W4Run> kW4Routes[] = {{"none", nullptr, -1, {}}, SMC_WINO4_ROUTES(SMC_WINO_ROUTE_ROW)};
+constexpr int kW4RouteCount = sizeof(kW4Routes) / sizeof(kW4Routes[0]);
+
+// ---- plan: the shape predicate and the kernel's two forms, from the call's arguments alone
+W4Plan plan_wino4(int n, int cin, int cout, int h, int w, bool has_s, const smc_conv_epilogue* epi) {
+    W4Plan pl{};
+    if (n < 1 || cin < W4K || cin % W4K) return pl;
+    if ((int64_t)n * cin * h * w * 4 >= (1LL << 31)) return pl;  // raw buffer offsets are 32-bit
+    if ((int64_t)cin * 36 * cout * 4 >= (1LL << 31)) return pl;
+    if (!(w % 64 == 0 && w >= 64 && h % 8 == 0 && h >= 8 && cout % 64 == 0 && cout >= 64)) return pl;
+    pl.gx = w / 64;
+    pl.gy = h / 8;
+    pl.ntn = cout / 64;
+    pl.items = (int64_t)n * pl.gx * pl.gy * pl.ntn;
+    pl.sm = has_s ? 1 : 2;
+    pl.ek = smc::epi_body(smc::epi_or_default(epi));
+    pl.route = smc::route_of(kW4Routes, K_wino4_kernel, pl.sm, pl.ek);
+    return pl;
 }
 
-// work item = 64 output channels x 32 tiles (2 tile rows x 16 tile columns = 8 x 64 outputs)
-bool w4_shape_ok(int cout, int h, int w) {
-    return w % 64 == 0 && w >= 64 && h % 8 == 0 && h >= 8 && cout % 64 == 0 && cout >= 64;
-}
+thread_local int g_w4_route = 0;
 
 }  // namespace
 
 SMC_API int smc_conv3x3_wino4_supported(int n, int cin, int cout, int h, int w) {
-    if (n < 1 || cin < W4K || cin % W4K) return 0;
-    if ((int64_t)n * cin * h * w * 4 >= (1LL << 31)) return 0;  // raw buffer offsets are 32-bit
-    if ((int64_t)cin * 36 * cout * 4 >= (1LL << 31)) return 0;
-    return w4_shape_ok(cout, h, w);
+    return plan_wino4(n, cin, cout, h, w, false, nullptr).route != 0;
+}
+
+SMC_API int smc_conv3x3_wino4_plan(int n, int cin, int cout, int h, int w, int has_style, const smc_conv_epilogue* epi,
+                                   int* route) {
+    const W4Plan pl = plan_wino4(n, cin, cout, h, w, has_style != 0, epi);
+    if (route) *route = pl.route;
+    return pl.route ? SMC_OK : SMC_ERR_UNSUPPORTED;
 }
 
 SMC_API int smc_wino4_weights_f32(const float* w, int cout, int cin, int flip, float* uw, void* stream) {
@@ -478,7 +500,9 @@ SMC_API int smc_conv3x3_wino4_f32(const float* x, int n, int cin, int h, int w, 
                                   const float* s_in, const smc_conv_epilogue* epi, void* stream) {
     g_w4_route = 0;
     SMC_CHECK(x && y && uw, "smc_conv3x3_wino4_f32: null pointer");
-    if (!smc_conv3x3_wino4_supported(n, cin, cout, h, w)) {
+    // ---- plan
+    const W4Plan pl = plan_wino4(n, cin, cout, h, w, s_in != nullptr, epi);
+    if (!pl.route) {
         smc::set_error("smc_conv3x3_wino4_f32: no Winograd F(4x4) kernel for n=%d cin=%d cout=%d %dx%d", n, cin, cout,
                        h, w);
         return SMC_ERR_UNSUPPORTED;
@@ -486,35 +510,20 @@ SMC_API int smc_conv3x3_wino4_f32(const float* x, int n, int cin, int h, int w, 
     SMC_CHECK((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(uw) & 15) == 0,
               "smc_conv3x3_wino4_f32: x / y / uw must be 16-B aligned");
-    smc_conv_epilogue e{};
-    e.mode = SMC_EPI_STORE; e.act = SMC_ACT_LINEAR; e.gain = 1.f; e.clamp = -1.f;
-    if (epi) e = *epi;
-    SMC_CHECK(e.mode >= SMC_EPI_STORE && e.mode <= SMC_EPI_AFFINE, "smc_conv3x3_wino4_f32: bad epilogue mode %d", e.mode);
-    SMC_CHECK((e.mode != SMC_EPI_PRELU && e.mode != SMC_EPI_PRELU_GRAD) || e.alpha_c,
-              "smc_conv3x3_wino4_f32: PReLU epilogue needs alpha_c");
-    SMC_CHECK(e.mode != SMC_EPI_PRELU_GRAD || e.act_ref, "smc_conv3x3_wino4_f32: PRELU_GRAD needs act_ref");
-    SMC_CHECK(!e.u_save || (reinterpret_cast<uintptr_t>(e.u_save) & 15) == 0, "smc_conv3x3_wino4_f32: u_save alignment");
+    const smc_conv_epilogue e = smc::epi_or_default(epi);
+    const int rc = smc::check_epilogue(e, "smc_conv3x3_wino4_f32", 16);
+    if (rc != SMC_OK) return rc;
     SMC_CHECK(!e.noise || ((reinterpret_cast<uintptr_t>(e.noise) & 15) == 0 && e.noise_nstride % 4 == 0),
               "smc_conv3x3_wino4_f32: noise must be 16-B aligned");
+    SMC_CHECK(pl.items < (1LL << 31), "smc_conv3x3_wino4_f32: grid too large");
+    // ---- prepare
     Wino4Params p{};
     p.x = x; p.n = n; p.cin = cin; p.h = h; p.w = w; p.y = y; p.cout = cout; p.uw = uw; p.s = s_in;
-    p.mode = e.mode; p.d = e.d; p.noise = e.noise; p.noise_nstride = e.noise_nstride;
-    p.noise_strength = e.noise_strength; p.bias = e.bias; p.act = e.act; p.alpha = e.alpha; p.gain = e.gain;
-    p.clamp = e.clamp; p.u_save = e.u_save;
-    p.ext = smc::epi_ext(epi);
-    p.gx = w / 64;
-    p.gy = h / 8;
-    p.ntn = cout / 64;
-    const int64_t items = (int64_t)n * p.gx * p.gy * p.ntn;
-    SMC_CHECK(items < (1LL << 31), "smc_conv3x3_wino4_f32: grid too large");
-    hipStream_t st = smc::as_stream(stream);
-    const bool modact_plain = p.mode == SMC_EPI_MODACT && !p.ext.residual;
-    if (modact_plain && p.act == SMC_ACT_LRELU && p.alpha >= 0.f && p.alpha <= 1.f && p.clamp >= 0.f)
-        launch_w4_s<1>(s_in != nullptr, p, items, st);
-    else if (modact_plain && p.act == SMC_ACT_LINEAR && p.clamp < 0.f)
-        launch_w4_s<2>(s_in != nullptr, p, items, st);
-    else
-        launch_w4_s<0>(s_in != nullptr, p, items, st);
+    smc::fill_epilogue(p, e);
+    p.gx = pl.gx; p.gy = pl.gy; p.ntn = pl.ntn;
+    // ---- launch
+    g_w4_route = pl.route;
+    kW4Routes[pl.route].run(pl, p, smc::as_stream(stream));
     return smc::check_launch("smc_conv3x3_wino4_f32");
 }
 
@@ -522,6 +531,4 @@ SMC_API int smc_conv3x3_wino4_last_route(void) { return g_w4_route; }
 
 SMC_API int smc_conv3x3_wino4_route_count(void) { return kW4RouteCount; }
 
-SMC_API const char* smc_conv3x3_wino4_route_name(int route) {
-    return route >= 0 && route < kW4RouteCount ? kW4RouteNames[route] : nullptr;
-}
+SMC_API const char* smc_conv3x3_wino4_route_name(int route) { return smc::route_name(kW4Routes, route); }

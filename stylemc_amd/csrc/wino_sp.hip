@@ -347,8 +347,6 @@ SMC_API int smc_conv3x3_wino_sp_f32(const float* x, int n, int cin, int h, int w
     hipLaunchKernelGGL(wino_sp_kernel, dim3((unsigned)s.nitems, (unsigned)s.nsplit), dim3(256), 0, st, p);
     const int rc = smc::check_launch("smc_conv3x3_wino_sp_f32");
     if (rc != SMC_OK) return rc;
-    smc_conv_epilogue e{};
-    e.mode = SMC_EPI_STORE; e.act = SMC_ACT_LINEAR; e.gain = 1.f; e.clamp = -1.f;
-    if (epi) e = *epi;
+    const smc_conv_epilogue e = smc::epi_or_default(epi);
     return smc_modconv_epilogue_f32(workspace, s.nsplit, p.split_stride, y, n, cout, h, w, &e, stream);
 }

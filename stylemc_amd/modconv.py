@@ -92,7 +92,6 @@ class PackedConv:
         self._x3 = {}
         self._cache = {}
         self._wino = {}
-        self._wino4 = {}
 
     def _planes(self, key, wk, cin, cout):
         if key not in self._x3:
@@ -116,31 +115,35 @@ class PackedConv:
             return None
         return [self._planes(("p", i), wk, self.cin, self.cout) for i, (_, _, _, wk) in enumerate(self.phases)]
 
-    def wino_weights(self, flip):
-        """Winograd F(2x2, 3x3) transformed taps (smc_wino_weights_f32) of the 3x3 'same' conv, built once on the
-        weights' device: flip 0 = the forward, 1 = the data gradient.  LayerSpec builds both eagerly for the layers
-        that take the Winograd path; a transform built here later is waited for before it is returned (the first
-        caller may be on a side stream while the next launch that reads it is on another one)."""
-        if flip not in self._wino:
+    def _wino_taps(self, symbol, per_pair, flip):
+        """The transformed taps of the 3x3 'same' conv (per_pair floats per channel pair, written by `symbol`), built
+        once on the weights' device: flip 0 = the forward, 1 = the data gradient.  LayerSpec builds both eagerly for
+        the layers that take the Winograd path; a transform built here later is waited for before it is returned (the
+        first caller may be on a side stream while the next launch that reads it is on another one)."""
+        if (symbol, flip) not in self._wino:
             W = self.wk_bwd  # [t][o][i] -> back to [o][i][3][3] on the same device
             w = W.reshape(3, 3, self.cout, self.cin).permute(2, 3, 0, 1).contiguous()
-            uw = torch.empty(16 * self.cin * self.cout, device=w.device, dtype=torch.float32)
-            _hip.call("smc_wino_weights_f32", w.data_ptr(), self.cout, self.cin, flip, uw.data_ptr(), _hip.stream())
+            uw = torch.empty(per_pair * self.cin * self.cout, device=w.device, dtype=torch.float32)
+            _hip.call(symbol, w.data_ptr(), self.cout, self.cin, flip, uw.data_ptr(), _hip.stream())
             torch.cuda.current_stream(w.device).synchronize()
-            self._wino[flip] = uw
-        return self._wino[flip]
+            self._wino[symbol, flip] = uw
+        return self._wino[symbol, flip]
+
+    def wino_weights(self, flip):
+        """Winograd F(2x2, 3x3) transformed taps (smc_wino_weights_f32, 16 per channel pair)."""
+        return self._wino_taps("smc_wino_weights_f32", 16, flip)
 
     def wino4_weights(self, flip):
-        """Winograd F(4x4, 3x3) transformed taps (smc_wino4_weights_f32, 36 per channel pair), same contract as
-        wino_weights."""
-        if flip not in self._wino4:
-            W = self.wk_bwd
-            w = W.reshape(3, 3, self.cout, self.cin).permute(2, 3, 0, 1).contiguous()
-            uw = torch.empty(36 * self.cin * self.cout, device=w.device, dtype=torch.float32)
-            _hip.call("smc_wino4_weights_f32", w.data_ptr(), self.cout, self.cin, flip, uw.data_ptr(), _hip.stream())
-            torch.cuda.current_stream(w.device).synchronize()
-            self._wino4[flip] = uw
-        return self._wino4[flip]
+        """Winograd F(4x4, 3x3) transformed taps (smc_wino4_weights_f32, 36 per channel pair)."""
+        return self._wino_taps("smc_wino4_weights_f32", 36, flip)
+
+    def path(self, n, flip, h, w):
+        """conv3x3_path() of the layer's forward (flip 0) or data gradient (flip 1: the channels exchanged) on n
+        [h, w] planes; "direct" for every layer that is no 3x3 stride-1 conv."""
+        if not (self.up == 1 and self.k == 3):
+            return "direct"
+        ci, co = (self.cout, self.cin) if flip else (self.cin, self.cout)
+        return conv3x3_path(n, ci, co, h, w)
 
     def fwd_phases(self, h, w):
         key = ("f", h, w)
@@ -251,6 +254,37 @@ def wino_flops(n, cin, cout, h, w):
     return 2.0 * n * cin * cout * (h // 2) * (w // 2) * 16
 
 
+def conv3x3_path(n, cin, cout, h, w):
+    """The kernel family of a 3x3 stride-1 pad-1 conv: "wino4" (F(4x4)) where it is picked, else "wino" (F(2x2))
+    where it has a kernel, else "direct" (the implicit GEMM).  The one statement of that order."""
+    if wino4_pick(n, cin, cout, h, w):
+        return "wino4"
+    if wino_ok(n, cin, cout, h, w):
+        return "wino"
+    return "direct"
+
+
+def conv3x3(x, out, P, flip, s=None, epi=None, out_planes=1):
+    """The stride-1 conv of an up = 1 layer on the family P.path() names: the forward (flip 0, x [n, cin, h, w] ->
+    out [n, cout, h, w]) or the data gradient (flip 1, the channels exchanged).  out_planes: the planes of out's size
+    the launch writes (2 with a saved u), for the timer's bytes -- input and output activations once, the family's
+    taps once; its FLOPs are the family's own."""
+    n, ci, h, w = x.shape
+    co = out.shape[1]
+    path = P.path(n, flip, h, w)
+    io_bytes = 4 * x.numel() + 4 * out.numel() * out_planes
+    if path == "wino4":
+        wino4(x, out, P.wino4_weights(flip), ci, co, s=s, epi=epi, alg_flops=wino4_flops(n, ci, co, h, w),
+              alg_bytes=io_bytes + 36 * 4 * ci * co)
+    elif path == "wino":
+        wino(x, out, P.wino_weights(flip), ci, co, s=s, epi=epi, alg_flops=wino_flops(n, ci, co, h, w),
+             alg_bytes=io_bytes + 16 * 4 * ci * co)
+    else:
+        phases, nph = P.bwd_phases(h, w) if flip else P.fwd_phases(h, w)[:2]
+        gemm(x, out, phases, nph, ci, co, s=s, epi=epi, alg_flops=conv_flops(n, ci, co, h, w, P.k * P.k),
+             alg_bytes=io_bytes + 4 * P.k * P.k * ci * co)
+
+
 # The up=2 layers whose transposed conv runs as the 4-phase split-bf16 kernel (32 / 64 output channels: the 512- and
 # 1024-px conv0) in one launch, smc_modconv_up2_f32: conv, 4x4 FIR and epilogue with the raw conv output T kept in
 # LDS instead of written to and re-read from HBM (bit-identical y / u).  Module switch, as WINOGRAD.
@@ -303,9 +337,7 @@ def fused_torgb_ok(spec, n, cin, h, w, cout_rgb, epi, has_u):
     gradient's layers keep the two launches), and the library's gate -- 32 output channels, 1..4 image channels, the
     lrelu epilogue, and a two-launch plan that runs unsplit at the planning batch."""
     P = spec.packed
-    if not (FUSED_TORGB and spec.up == 1 and P.k == 3 and not has_u):
-        return False
-    if wino4_pick(n, cin, P.cout, h, w) or not wino_ok(n, cin, P.cout, h, w):
+    if not (FUSED_TORGB and not has_u and P.path(n, 0, h, w) == "wino"):
         return False
     return bool(_hip.load().smc_modconv_conv1_torgb_supported(n, cin, P.cout, h, w, cout_rgb, ctypes.byref(epi)))
 
@@ -361,14 +393,14 @@ class LayerSpec:
             # runs the original-image synthesis on a side stream): build the Winograd transforms of a Winograd
             # layer now, and let every packing kernel finish before another stream can read the packed weights
             direct = [True, True]   # forward, data gradient on the direct implicit GEMM (split-bf16 planes)
-            if resolution is not None and up == 1 and P.k == 3:
-                for flip, (ci, co) in enumerate([(P.cin, P.cout), (P.cout, P.cin)]):
-                    if wino4_pick(1, ci, co, resolution, resolution):
+            if resolution is not None:
+                for flip in (0, 1):
+                    path = P.path(1, flip, resolution, resolution)
+                    if path == "wino4":
                         P.wino4_weights(flip)
-                        direct[flip] = False
-                    elif wino_ok(1, ci, co, resolution, resolution):
+                    elif path == "wino":
                         P.wino_weights(flip)
-                        direct[flip] = False
+                    direct[flip] = path == "direct"
             # the split-bf16 planes of the directions that take the direct GEMM, built here (one wait below) rather than
             # on first use inside a step, where the build's host wait would stall whichever stream reached it first
             if resolution is not None:
@@ -429,16 +461,8 @@ def _modconv_fwd(ctx, x, styles, spec, noise, strength, gain, clamp, need_dx, ne
         fused_torgb(x, y, P.wino_weights(0), cin, P.cout, styles, epi, s_rgb, w_rgb, b_rgb, clamp_rgb, rgb,
                     alg_flops=wino_flops(n, cin, P.cout, h, w),
                     alg_bytes=4 * x.numel() + _nbytes(y) + 4 * rgb.numel() + 16 * 4 * cin * P.cout)
-    elif spec.up == 1 and P.k == 3 and wino4_pick(n, cin, P.cout, h, w):
-        wino4(x, y, P.wino4_weights(0), cin, P.cout, s=styles, epi=epi, alg_flops=wino4_flops(n, cin, P.cout, h, w),
-              alg_bytes=4 * x.numel() + 4 * y.numel() * (2 if u is not None else 1) + 36 * 4 * cin * P.cout)
-    elif spec.up == 1 and P.k == 3 and wino_ok(n, cin, P.cout, h, w):
-        wino(x, y, P.wino_weights(0), cin, P.cout, s=styles, epi=epi, alg_flops=wino_flops(n, cin, P.cout, h, w),
-             alg_bytes=4 * x.numel() + 4 * y.numel() * (2 if u is not None else 1) + 16 * 4 * cin * P.cout)
     elif spec.up == 1:
-        gemm(x, y, phases, nph, cin, P.cout, s=styles, epi=epi,
-             alg_flops=conv_flops(n, cin, P.cout, r_h, r_w, P.k * P.k),
-             alg_bytes=4 * x.numel() + 4 * y.numel() * (2 if u is not None else 1) + wbytes)
+        conv3x3(x, y, P, 0, s=styles, epi=epi, out_planes=2 if u is not None else 1)
     elif fused_up_ok(spec, n, cin, h, w):
         fused_up(x, y, phases, nph, cin, P.cout, styles, epi,
                  alg_flops=conv_flops(n, cin, P.cout, h, w, 9),
@@ -520,18 +544,13 @@ def _modconv_bwd(ctx, saved, gy, need_dx, need_ds, g=None):
     else:
         ebw = _epilogue(_hip.EPI_STORE)
         out = dxs
-    g_bytes = 4 * g.numel() if spec.up == 1 else 4 * n * P.cout * (2 * h + 1) * (2 * w + 1)
-    out_bytes = 4 * out.numel() * (2 if (need_dx and need_ds) else 1)
-    if spec.up == 1 and P.k == 3 and wino4_pick(n, P.cout, cin, h, w):
-        wino4(g, out, P.wino4_weights(1), P.cout, cin, epi=ebw, alg_flops=wino4_flops(n, P.cout, cin, h, w),
-              alg_bytes=g_bytes + out_bytes + 36 * 4 * cin * P.cout)
-    elif spec.up == 1 and P.k == 3 and wino_ok(n, P.cout, cin, h, w):
-        wino(g, out, P.wino_weights(1), P.cout, cin, epi=ebw, alg_flops=wino_flops(n, P.cout, cin, h, w),
-             alg_bytes=g_bytes + out_bytes + 16 * 4 * cin * P.cout)
-    else:
+    out_planes = 2 if (need_dx and need_ds) else 1
+    if spec.up == 1:
+        conv3x3(g, out, P, 1, epi=ebw, out_planes=out_planes)
+    else:   # the stride-2 gather over dT (of its pitched rows the conv reads the 2 w + 1 columns)
         phases, nph = P.bwd_phases(h, w)
-        gemm(g, out, phases, nph, P.cout, cin, epi=ebw, alg_flops=conv_flops(n, P.cout, cin, h, w, P.k * P.k),
-             alg_bytes=g_bytes + out_bytes + 4 * P.k * P.k * cin * P.cout)
+        gemm(g, out, phases, nph, P.cout, cin, epi=ebw, alg_flops=conv_flops(n, P.cout, cin, h, w, 9),
+             alg_bytes=4 * n * P.cout * (2 * h + 1) * (2 * w + 1) + 4 * out.numel() * out_planes + 4 * 9 * cin * P.cout)
     ds = None
     if need_ds:
         ds = torch.empty(n, cin, device=x.device, dtype=torch.float32)

@@ -73,6 +73,26 @@ def test_wino_shape_support_without_gpu():
     assert lib.smc_conv3x3_wino_supported(16, 512, 512, 256, 256) == 0  # input >= 2 GiB (32-bit buffer offsets)
 
 
+def test_wino_plan_queries_without_gpu():
+    """smc_conv3x3_wino_plan / smc_conv3x3_wino4_plan are declared, bound and exported, and are host logic: the route
+    a call would report, SMC_ERR_UNSUPPORTED (2) with route 0 where *_supported is 0; NULL result pointers are allowed."""
+    lib = _hip.load()
+    for name in ("smc_conv3x3_wino_plan", "smc_conv3x3_wino4_plan"):
+        assert name in declared_symbols() and name in _hip.exported_symbols()
+    route, flags, ns = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    out = (ctypes.byref(route), ctypes.byref(flags), ctypes.byref(ns))
+    assert lib.smc_conv3x3_wino_plan(4, 32, 32, 1024, 1024, 0, None, 0, *out) == 0
+    assert lib.smc_conv3x3_wino_route_name(route.value) == b"wino_kernel<32,2,0>" and (flags.value, ns.value) == (0, 1)
+    assert lib.smc_conv3x3_wino_plan(4, 512, 512, 16, 16, 0, None, 0, *out) == 2       # w < 32
+    assert (route.value, flags.value, ns.value) == (0, 0, 0)
+    assert lib.smc_conv3x3_wino_plan(4, 32, 32, 1024, 1024, 1, None, 0, None, None, None) == 0
+    assert lib.smc_conv3x3_wino4_plan(4, 64, 64, 512, 512, 1, None, ctypes.byref(route)) == 0
+    assert lib.smc_conv3x3_wino4_route_name(route.value) == b"wino4_kernel<1,0>"
+    assert lib.smc_conv3x3_wino4_plan(4, 32, 32, 1024, 1024, 1, None, ctypes.byref(route)) == 2   # cout % 64
+    assert route.value == 0
+    assert lib.smc_conv3x3_wino4_plan(4, 64, 64, 512, 512, 0, None, None) == 0
+
+
 def test_dd_workspace_queries_without_gpu():
     """The epilogue backward kernels take their dd partials from a caller-owned workspace (no allocation inside the
     library): the queries are host logic, and a call that needs partials but gets no workspace fails

@@ -1,6 +1,7 @@
 """The Winograd entry points' host-side predicates (no GPU: the library loads without one) against a Python statement
 of the rules include/stylemc_hip.h gives (tests/wino_cases.py), and the case table of tests/test_gpu_wino_routes.py
 against those rules -- a table that drifts fails here, before any GPU run."""
+import ctypes
 import itertools
 
 from stylemc_amd import _hip
@@ -70,6 +71,119 @@ def test_wino_case_table_follows_the_rules():
             if not c.ws:   # no workspace passed: neither a split nor a fold may be planned for the launch
                 assert flags == 0, c.id
     assert wc.FOLD == _hip.ROUTE_WINO_FOLD and wc.SPLIT == _hip.ROUTE_SPLIT_K
+
+
+def _form_epilogue(form, h, w):
+    """The smc_conv_epilogue of a FORMS entry as the plan query reads it: the scalar fields, and an aligned non-NULL
+    placeholder for every operand the form sets (the query reads no memory behind a pointer)."""
+    f = wc.FORMS[form]
+    e = _hip.ConvEpilogue()
+    e.mode = getattr(_hip, "EPI_" + f["mode"])
+    e.act, e.alpha, e.gain, e.clamp = (_hip.ACT_CODES[f.get("act", "linear")], f.get("alpha", 0.0), f.get("gain", 1.0),
+                                       f.get("clamp", -1.0))
+    for field, key in (("d", "d"), ("noise", "noise"), ("noise_strength", "strength"), ("bias", "bias"),
+                       ("u_save", "u_save"), ("scale_c", "scale_c"), ("alpha_c", "alpha_c"), ("act_ref", "act_ref"),
+                       ("residual", "residual")):
+        if f.get(key):
+            setattr(e, field, 256)
+    e.noise_nstride = h * w if f.get("noise") == "img" else 0
+    e.residual_stride = f.get("residual") or 0
+    return e
+
+
+def _library_plan(lib, fam, n, cin, cout, h, w, style, form, nb):
+    """(return code, route name, flags, K splits) of smc_conv3x3_wino_plan / smc_conv3x3_wino4_plan."""
+    e = _form_epilogue(form, h, w) if isinstance(form, str) else form   # a form's name, an epilogue or None
+    epi = ctypes.byref(e) if e is not None else None
+    route, flags, ns = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    if fam == 2:
+        rc = lib.smc_conv3x3_wino_plan(n, cin, cout, h, w, int(style), epi, nb, ctypes.byref(route),
+                                       ctypes.byref(flags), ctypes.byref(ns))
+    else:
+        rc = lib.smc_conv3x3_wino4_plan(n, cin, cout, h, w, int(style), epi, ctypes.byref(route))
+        flags.value, ns.value = 0, 1 if rc == 0 else 0
+    return rc, wc.route_name(fam, route.value), flags.value, ns.value
+
+
+def test_library_plan_reaches_the_recorded_routes():
+    """The library's own plan (the host-only query, no device call) of every table case is the (route, flags, K
+    splits) recorded from its GPU launch -- with the workspace the size query asks for where the case passes one."""
+    lib = _hip.load()
+    assert lib.smc_set_wino_x3(0) == 0
+    for c in wc.CASES:
+        nb = lib.smc_conv3x3_wino_workspace_size(c.n, c.cin, c.cout, c.h, c.w) if c.ws else 0
+        rc, name, flags, ns = _library_plan(lib, c.fam, c.n, c.cin, c.cout, c.h, c.w, c.style, c.epi, nb)
+        assert rc == 0 and (name, flags, ns) == wc.EXPECTED[c.id], (c.id, rc, name, flags, ns)
+
+
+def test_library_plan_equals_the_restated_rules():
+    """Over the shape grid of the workspace test x style x workspace offered x every epilogue form (and the NULL
+    epilogue), the library's plan is what the restated rules give: wino_workspace, wino_nsplit, epilogue_body and the
+    naming rule of planned_route."""
+    lib = _hip.load()
+    assert lib.smc_set_wino_x3(0) == 0
+    forms = [None] + list(wc.FORMS)
+    checked = 0
+    for n, cin, cout, h, w in itertools.product((1, 2, 3, 4, 16), CIN, COUT, (4, 8, 16, 32, 64), (32, 64, 96, 128)):
+        ok2, ok4 = wc.wino_supported(n, cin, cout, h, w), wc.wino4_supported(n, cin, cout, h, w)
+        if not ok2:
+            assert _library_plan(lib, 2, n, cin, cout, h, w, True, None, 0) == (2, "none", 0, 0), (n, cin, cout, h, w)
+        if not ok4:
+            assert _library_plan(lib, 4, n, cin, cout, h, w, True, None, 0)[:2] == (2, "none"), (n, cin, cout, h, w)
+        if not (ok2 or ok4):
+            continue
+        need = lib.smc_conv3x3_wino_workspace_size(n, cin, cout, h, w)
+        epis = {form: _form_epilogue(form, h, w) if form is not None else None for form in forms}
+        for form, style, ws in itertools.product(forms, (False, True), (False, True)):
+            ek = wc.epilogue_body(form) if form is not None else 0
+            if ok2:
+                c = wc.Case("grid", 2, n, cin, cout, h, w, form, style, 0, ws)
+                # (planned_route reads the form through epilogue_body: NULL is the plain store, EK 0)
+                want = wc.planned_route(c._replace(epi=form or "store"))
+                got = _library_plan(lib, 2, n, cin, cout, h, w, style, epis[form], need if ws else 0)
+                assert got == (0,) + want, (c, got, want)
+                if ws and need > 0:   # a workspace one byte short is not used at all
+                    short = _library_plan(lib, 2, n, cin, cout, h, w, style, epis[form], need - 1)
+                    assert short == (0,) + wc.planned_route(c._replace(epi=form or "store", ws=False)), (c, short)
+                checked += 1
+            if ok4 and not ws:
+                got = _library_plan(lib, 4, n, cin, cout, h, w, style, epis[form], 0)
+                assert got == (0, f"wino4_kernel<{1 if style else 2},{ek}>", 0, 1), (n, cin, cout, h, w, form, style)
+                checked += 1
+    assert checked > 10000
+
+
+def test_library_plan_in_the_split_bf16_mode():
+    """smc_set_wino_x3(1) / (2): the 32 -> 32-channel TC 32 shape with its workspace plans the split-bf16 kernel for the
+    MODACT lrelu form (mode 2: also for the linear form), and the fused conv1 + ToRGB launch leaves such a shape to the
+    two-launch path.  Without the workspace, with unaligned noise or for another form the fp32 kernel keeps the call."""
+    lib = _hip.load()
+    shape = (2, 32, 32, 8, 64)
+    try:
+        for mode in (1, 2):
+            lib.smc_set_wino_x3(mode)
+            nb = lib.smc_conv3x3_wino_workspace_size(*shape)
+            assert nb == 2 * 16 * 3 * 2 * 4 * 16 * 8 * 2   # the planes (96 KB per image) exceed the folded taps
+            for style in (False, True):
+                assert _library_plan(lib, 2, *shape, style, "modact_lrelu", nb) == (0, "wino_x3r_kernel<1>", 0, 1)
+                lin = _library_plan(lib, 2, *shape, style, "modact_linear_bwd", nb)
+                assert lin == (0, "wino_x3r_kernel<2>" if mode == 2 else "wino_kernel<32,2,2>",
+                               wc.FOLD if style and mode == 1 else 0, 1), (mode, style, lin)
+                assert _library_plan(lib, 2, *shape, style, "modact_lrelu", 0) == \
+                    (0, f"wino_kernel<32,{1 if style else 2},1>", 0, 1)
+            assert _library_plan(lib, 2, *shape, False, "store", nb) == (0, "wino_kernel<32,2,0>", 0, 1)
+            e = _form_epilogue("modact_lrelu", 8, 64)
+            e.noise = 260   # not 16-B aligned: the fp32 kernel
+            route = ctypes.c_int(-1)
+            assert lib.smc_conv3x3_wino_plan(*shape, 0, ctypes.byref(e), nb, ctypes.byref(route), None, None) == 0
+            assert wc.route_name(2, route.value) == "wino_kernel<32,2,1>"
+            assert lib.smc_modconv_conv1_torgb_supported(*shape, 3, None) == 0
+            assert lib.smc_modconv_conv1_torgb_workspace_size(*shape) == 0
+            assert lib.smc_modconv_conv1_torgb_supported(2, 64, 32, 8, 64, 3, None) == 1   # (cin 64: not that kernel's)
+    finally:
+        lib.smc_set_wino_x3(0)
+    assert lib.smc_modconv_conv1_torgb_supported(*shape, 3, None) == 1
+    assert lib.smc_conv3x3_wino_workspace_size(*shape) == sum(wc.wino_workspace(*shape))
 
 
 def test_wino_case_table_covers_the_issue_list():

@@ -11,19 +11,20 @@ A case is (id, fam, n, cin, cout, h, w, epi, style, flip, ws):
   flip      1: the taps of the data gradient (smc_wino*_weights_f32 flip = 1 of a [cin][cout][3][3] forward weight)
   ws        F(2x2) only: the call passes the workspace smc_conv3x3_wino_workspace_size() asks for
 
-The guards the routes are read off (wino.hip; SMC_WINO_FOLD 1, split target 512):
+The guards the routes are read off (plan_wino() in wino.hip; SMC_WINO_FOLD 1, split target 512):
   TC     wino_tc(): `for (tc = 32; tc >= 16; tc /= 2) if ((w / 2) % tc == 0 && (h / 2) % (WBT / tc) == 0)`
          -> 32 where w % 64 == 0 and h % 4 == 0, else 16 where w % 32 == 0 and h % 8 == 0 (so TC 16 means w % 64 == 32)
-  fold   `if (SMC_WINO_FOLD && s_in && fold_bytes > 0 && ws_ok)`, fold_bytes > 0 iff cin * cout <= 128 * 128: the
-         launch then runs SM = 2 (`s_in = nullptr`) with SMC_ROUTE_WINO_FOLD
-  SM     `launch_wino_s: if (has_s) launch_wino_tc<1, EK> else launch_wino_tc<2, EK>`
-  split  `if (split_bytes > 0 && ws_ok)` -> EK 3, SMC_ROUTE_SPLIT_K; wino_nsplit(): `while (items * ns < 512 &&
+  fold   `pl.fold = has_s && pl.fold_bytes > 0 && ws_ok`, fold_bytes > 0 iff cin * cout <= 128 * 128: the launch then
+         runs SM = 2 with SMC_ROUTE_WINO_FOLD
+  SM     `pl.sm = has_s && !pl.fold ? 1 : 2`
+  split  `if (pl.split_bytes > 0 && ws_ok)` -> EK 3, SMC_ROUTE_SPLIT_K; the split count: `while (items * ns < 512 &&
          nsteps % (2 * ns) == 0 && nsteps / (2 * ns) >= 8) ns *= 2` -- cin >= 128 for two splits of 8 steps
-  EK     `modact_plain = mode == MODACT && !residual`; `ek1 = modact_plain && act == LRELU && 0 <= alpha <= 1 &&
-         clamp >= 0`; `ek2 = modact_plain && act == LINEAR && clamp < 0`; else 0.  (Neither scale_c nor a NULL operand is
+  EK     smc::epi_body() (wino_host.hpp): `modact_plain = mode == MODACT && !residual`; 1 where `modact_plain && act ==
+         LRELU && 0 <= alpha <= 1 && clamp >= 0`; 2 where `modact_plain && act == LINEAR && clamp < 0`; else 0.
+         (Neither scale_c nor a NULL operand is
          part of the guard: MODACT lrelu + clamp with scale_c, or with d = bias = strength = NULL, runs EK 1;
          the table holds each of the two both ways, with the clamp (EK 1) and with clamp = -1 (the generic body).)
-F(4x4) has the SM and EK guards only (launch_w4_s; the same ek1 / ek2 conditions).
+F(4x4) has the SM and EK guards only (plan_wino4() in wino4.hip; the same epi_body()).
 
 Reference and bounds.  u64 is the fp64 conv of the fp32 operands (x s, W), B = conv(|W|, |x s|) the sum of the
 magnitudes of its products, TOL / REL the project's Winograd bounds (F(2x2): 2e-6 B elementwise, 1e-6 relative norm,

@@ -40,7 +40,10 @@ void launch_i(const WinoParams& p, int r, int n, int c) {
     q.ntn = c / WBO;
     const int items = n * q.gx * q.gy * q.ntn;
     if (PERSIST) {
-        launch_wino<TC, SM, 0>(q, items, 0);
+        WinoPlan pl{};
+        pl.items = items;
+        pl.nsplit = 1;
+        run_wino_kernel<TC, SM, 0>(pl, q, nullptr, 0, 0);   // the library's launcher (the route table's)
     } else {
         auto kern = &wino_kernel<TC, SM, 0, 0, PROBE>;
         hipLaunchKernelGGL(kern, dim3(items), dim3(256), 0, 0, q);
