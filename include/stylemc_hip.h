@@ -716,6 +716,41 @@ int smc_conv_s2_grouped_f32(const float* x, int64_t x_sample_stride, int64_t x_g
                             int h, int w, const float* wk, const int* taps, int ntaps, const float* bias, float alpha,
                             float* y, int cout, float* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Face landmarks (MTCNN detector, MobileNet-GDConv regressor): depthwise convolution, ceil-mode max-pool and the
+ * crop + bilinear resize + normalise of a face box.  Inference only, fp32, no atomics and a fixed summation order
+ * (bit-identical from run to run), 64-bit plane offsets.  Added under ABI version 6 without a version bump: callers
+ * detect these entry points by symbol.  Every limit below is checked on the host before any launch (SMC_ERR_INVALID).
+ *
+ * smc_dwconv_f32:  y[n][c] = act(scale_c[c] * (w[c] * x[n][c]) + shift_c[c])   (cross-correlation, as nn.Conv2d with
+ * groups = channels; eval-mode BatchNorm folded into scale_c / shift_c, either may be NULL = 1 / 0).
+ *   x [n][c][in_h][in_w], w [c][k][k], y [n][c][oh][ow].  Two forms:
+ *     k = 3, pad = 1, stride 1 or 2: any plane >= 1 x 1, out = (in + 2 - 3) / stride + 1;
+ *     pad = 0, stride 1, k == in_h == in_w, 2 <= k <= 8 (the "global" depthwise layer of MobileNet_GDConv): out 1 x 1.
+ *   n * c <= 2^31 - 1, sides <= 32768.  16-byte loads and stores are used where x and y are 16-byte aligned and in_w is
+ *   a multiple of 4 * stride; the results do not depend on that. */
+#define SMC_DW_ACT_LINEAR 0
+#define SMC_DW_ACT_RELU6 1 /* min(max(z, 0), 6) */
+int smc_dwconv_supported(int n, int c, int in_h, int in_w, int k, int stride, int pad);
+int smc_dwconv_f32(const float* x, int n, int c, int in_h, int in_w, const float* w, int k, int stride, int pad,
+                   const float* scale_c, const float* shift_c, int act, float* y, void* stream);
+
+/* nn.MaxPool2d(k, stride, ceil_mode = True), pad 0, for (k, stride) = (2, 2) or (3, 2) (MTCNN/get_nets.py):
+ * x [planes][in_h][in_w] -> y [planes][oh][ow], out = ceil((in - k) / stride) + 1, the last window clipped at the
+ * border; in_h, in_w >= k.  NaN propagates as in torch. */
+int smc_maxpool2d_f32(const float* x, int64_t planes, int in_h, int in_w, int k, int stride, float* y, void* stream);
+
+/* One face crop per image, from a generator image to the regressor's input, in one launch:
+ *   v   = denorm ? clamp(img * 127.5 + 128, 0, 255) : img            (denorm_img, float: no uint8 step)
+ *   r   = bilinear(v[:, y1:y2, x1:x2] -> out_size x out_size)        (align_corners = False, no antialias; the source
+ *                                                                     coordinate as torch computes it in fp32)
+ *   out = (r / 255 - mean[c]) / std[c],  or r itself where mean3 and std3 are both NULL (crop_face's own output)
+ * img [n][3][in_h][in_w], boxes [n][4] int32 ON THE DEVICE as (x1, y1, x2, y2) with exclusive ends, out
+ * [n][3][out_size][out_size]; mean3 / std3: HOST arrays of 3 floats (std != 0), both or neither.  A box is clipped to
+ * the image by the kernel (at least one pixel is kept), so no box can make it read outside the planes. */
+int smc_crop_bilinear_norm_f32(const float* img, int n, int in_h, int in_w, const int* boxes, int out_size, int denorm,
+                               const float* mean3, const float* std3, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

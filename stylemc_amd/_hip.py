@@ -19,6 +19,7 @@ c_int, c_int64, c_float, c_void_p, c_char_p = ctypes.c_int, ctypes.c_int64, ctyp
 ACT_CODES = {"linear": 1, "relu": 2, "lrelu": 3, "tanh": 4, "sigmoid": 5, "elu": 6, "selu": 7, "softplus": 8,
              "swish": 9}
 EPI_STORE, EPI_MODACT, EPI_PRELU, EPI_PRELU_GRAD, EPI_AFFINE = 0, 1, 2, 3, 4
+DW_ACT_LINEAR, DW_ACT_RELU6 = 0, 1
 ROUTE_SPLIT_K, ROUTE_PER_SAMPLE, ROUTE_PRESCALE, ROUTE_WSAMPLE = 1, 2, 4, 8
 ROUTE_WINO_FOLD = 16
 ROUTE_DD_PARTIALS = 32
@@ -175,6 +176,10 @@ _SIGS = {
     "smc_conv_s2_grouped_workspace_size": (c_int64, [c_int] * 7),
     "smc_conv_s2_grouped_f32": (c_int, [P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P,
                                         c_float, P, c_int, P, c_int64, P]),
+    "smc_dwconv_supported": (c_int, [c_int] * 7),
+    "smc_dwconv_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, c_int, P, P]),
+    "smc_maxpool2d_f32": (c_int, [P, c_int64, c_int, c_int, c_int, c_int, P, P]),
+    "smc_crop_bilinear_norm_f32": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P]),
 }
 
 _lib = None

@@ -15,7 +15,9 @@ What is restated and what is not:
                  start_from_latent_avg), the ``encoder.``-prefixed state_dict keys, ``latent_avg``.  Loaded with
                  ``weights_only=True``.  Without --checkpoint the seeded synthetic encoder is used, as the other CLIs do
                  with ``--network synthetic``.
-  alignment      infer.py:96-105 (dlib landmarks + align_face) is not built: pass an already aligned face crop.
+  alignment      infer.py:96-105 aligns with dlib landmarks; here ``--align`` runs stylemc_amd.align_faces first (MTCNN +
+                 MobileNet-GDConv landmarks, the same FFHQ align_face), as the reference's own align_faces.py does.
+                 Without ``--align`` the image is taken as an already aligned face crop.
   decoder        the rosinality generator only renders the inversion for display (infer.py:127-133); W does not need it.
 """
 import os
@@ -76,19 +78,31 @@ def invert(net, image, device="cuda"):
 def _cli():
     import click
 
-    @click.command(help="Invert an ALIGNED face image to W+ with the e4e encoder on the HIP kernels and write "
-                        "np.savez(out_file, w=[1, 18, 512]) for `w_s w_s_converter`.  Face alignment (dlib) is not "
-                        "built: the image is taken as already aligned and is resized to 256x256.")
-    @click.option("--input_image", type=str, required=True, help="aligned face image (any format PIL opens)")
+    @click.command(help="Invert a face image to W+ with the e4e encoder on the HIP kernels and write "
+                        "np.savez(out_file, w=[1, 18, 512]) for `w_s w_s_converter`.  The image is an aligned face "
+                        "crop (taken as it is, resized to 256x256), or with --align any photograph of a face, which is "
+                        "aligned first (stylemc_amd.align_faces).")
+    @click.option("--input_image", type=str, required=True,
+                  help="aligned face image, or with --align a photograph (any format PIL opens)")
+    @click.option("--align", is_flag=True, help="detect the face and its landmarks and FFHQ-align the image first")
+    @click.option("--mobilenet_checkpoint", type=str, default=None,
+                  help="--align: landmark regressor checkpoint or 'synthetic' (default: align_faces' file name)")
+    @click.option("--mtcnn_weights", type=str, default=None,
+                  help="--align: MTCNN weights directory or 'synthetic' (default: align_faces' directory)")
     @click.option("--checkpoint", type=str, default=None,
                   help="e4e / pSp checkpoint (e4e_ffhq_encode.pt); default: the seeded synthetic encoder")
     @click.option("--out_file", type=str, default="encoder4editing/projected_w.npz", show_default=True)
-    def main(input_image, checkpoint, out_file):
+    def main(input_image, align, mobilenet_checkpoint, mtcnn_weights, checkpoint, out_file):
         from PIL import Image
         if not os.path.exists(input_image):
             raise SystemExit(f"input image not found: {input_image}")
+        image = Image.open(input_image)
+        if align:
+            from .. import align_faces
+            image = align_faces.align_image(image, checkpoint=mobilenet_checkpoint or align_faces.DEFAULT_CHECKPOINT,
+                                            mtcnn_weights=mtcnn_weights or align_faces.DEFAULT_MTCNN)
         net = load_encoder(checkpoint)
-        w = invert(net, Image.open(input_image))
+        w = invert(net, image)
         os.makedirs(os.path.dirname(out_file) or ".", exist_ok=True)
         np.savez(out_file, w=w.cpu().numpy())
         print(f"wrote {out_file}: w {tuple(w.shape)}")

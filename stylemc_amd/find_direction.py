@@ -13,7 +13,12 @@ the directional CLIP loss normalises a zero feature difference (clip_loss.py:29-
 then poisons every later step.  Runs therefore start from ``initial_delta(seed, init_std)``, a seeded
 N(0, init_std) direction (--init_std 0 reproduces the literal zero start).
 Landmarks: the reference computes that term under torch.no_grad (:90), so it never changes the
-direction; a non-zero --landmarks_loss_coef is accepted and ignored with a warning.
+direction.  With --mobilenet_checkpoint and --mtcnn_weights present (or 'synthetic') and a non-zero
+--landmarks_loss_coef it is computed here too, but only for the iterations whose line is printed, on the
+printing rank, from a forward-only re-render of that iteration's global batch with the pre-update
+direction (DirectionFinder.landmarks_value): the step itself is unchanged.  The reference evaluates it
+every iteration; it carries no gradient, so the direction is identical.  Without the weights a non-zero
+coefficient is accepted and ignored with a warning, and the term prints as 0.
 generate_image is called with the missing ``device`` fixed (:309,312 raise TypeError as shipped).
 
 Multi-GPU: every rank draws the same i, takes its contiguous slice of the global batch and returns one row per
@@ -117,6 +122,120 @@ def compute_loss(img, original_img, transf, mean, std, device, clip_loss_type, c
     loss = identity_loss + clip_alignment_loss + l2
     return loss, {"clip_loss": clip_alignment_loss, "identity_loss": identity_loss, "landmarks_loss": 0.0,
                   "l2_loss": l2}
+
+
+def denorm_img(img):
+    """[3, H, W] generator image in [-1, 1] -> [H, W, 3] in 0..255, float (find_direction.py:44-46)."""
+    return (img.permute(1, 2, 0) * 127.5 + 128).clamp(0, 255)
+
+
+def _regress(planes, boxes, denorm, model, mean, std, out_size):
+    """The crops of ``boxes`` out of ``planes`` [n, 3, H, W] in one smc_crop_bilinear_norm_f32 launch, one regressor call,
+    and the outputs (fractions of the crop) scaled by the clipped window's height and moved to its corner: [n, 68, 2]."""
+    from . import mobilenet_hip
+    boxes_t = torch.tensor(boxes, dtype=torch.int32, device=planes.device)
+    crops = mobilenet_hip.crop_bilinear_norm(planes, boxes_t, out_size, mean.reshape(-1).tolist(),
+                                            std.reshape(-1).tolist(), denorm=denorm)
+    with torch.no_grad():
+        landmarks = model(crops)
+    landmarks = landmarks.view(landmarks.size(0), -1, 2)
+    side = (boxes_t[:, 3] - boxes_t[:, 1]).to(landmarks.dtype).view(-1, 1, 1)
+    return landmarks * side + boxes_t[:, None, 0:2].to(landmarks.dtype)
+
+
+def _first_face_boxes(images, device, mtcnn, detect_kwargs):
+    """crop_box of faces[0] -- the first face, not the best-scoring one, as the reference takes it -- per [H, W, 3] image
+    of 0..255 values (detect_faces works on its uint8 copy, on the host); None when any image has no face."""
+    from .MTCNN import detect_faces
+    from .warp_images import crop_box
+    boxes = []
+    for im in images:
+        faces, _ = detect_faces(im, device=device, nets=mtcnn, **detect_kwargs)
+        if not len(faces):
+            return None
+        boxes.append(crop_box(im.size(1), im.size(0), faces[0])[0])
+    return boxes
+
+
+def detect_landmarks(img, model, device, mean, std, out_size=224, mtcnn=None, **detect_kwargs):
+    """68 landmarks per image, in image pixels (find_direction.py:55-97).  img: an [H, W, 3] tensor of 0..255 values
+    (denorm_img's output) or a list of them; model: the regressor ([n, 3, out_size, out_size] -> [n, 136]); mtcnn: the
+    detector's nets (MTCNN.detector.default_nets when None); detect_kwargs go to detect_faces (min_face_size, thresholds,
+    nms_thresholds; the reference uses its defaults).  Returns [n, 68, 2], or None when any image has no face.
+    (compute_landmarks_loss does not come through here: it crops the generator batch itself, see
+    detect_landmarks_batch.)"""
+    imgs = img if isinstance(img, list) else [img]
+    boxes = _first_face_boxes(imgs, device, mtcnn, detect_kwargs)
+    if boxes is None:
+        return None
+    planes = torch.stack([im.permute(2, 0, 1) for im in imgs]).to(device, torch.float32)
+    return _regress(planes, boxes, False, model, mean, std, out_size)
+
+
+def detect_landmarks_batch(img_batch, model, device, mean, std, out_size=224, mtcnn=None, **detect_kwargs):
+    """detect_landmarks for a generator batch [n, 3, H, W] in [-1, 1].  Only the detector sees a denormed copy, and only
+    as uint8 (it truncates to uint8 anyway, detector.py:24-25); the crop kernel reads the batch itself and applies
+    denorm_img to the taps it interpolates, so no float 0..255 image and no stacked copy is made."""
+    with torch.no_grad():
+        u8 = [denorm_img(x).to(torch.uint8) for x in img_batch]
+    boxes = _first_face_boxes(u8, device, mtcnn, detect_kwargs)
+    if boxes is None:
+        return None
+    return _regress(img_batch.to(device, torch.float32), boxes, True, model, mean, std, out_size)
+
+
+def compute_landmarks_loss(gen_img_batch, original_img_batch, landmarks_loss, landmarks_loss_coef, model, device, mean,
+                           std, img_size=224, mtcnn=None, **detect_kwargs):
+    """coef * landmarks_loss(landmarks(original), landmarks(edited)) (find_direction.py:125-145), no gradient.
+    Any image without a face makes the term 0: no face in an original image returns 0; no face in an edited image
+    falls back to landmarks2 = landmarks1, whose distance is 0.  Deviations: where the originals have no face but the
+    edited images do, the reference calls the loss on None and dies of an uncaught TypeError; here that is 0 too.  The
+    reference's bare ``except`` turns ANY failure into 0 or the fallback (a missing weight file included); here only the
+    detector's own "nothing found" errors (ValueError / IndexError from empty box arrays) are, and everything else --
+    a failed kernel call, a missing file -- propagates."""
+    if landmarks_loss_coef == 0:
+        return 0
+    with torch.no_grad():
+        try:
+            landmarks1 = detect_landmarks_batch(original_img_batch, model, device, mean, std, img_size, mtcnn=mtcnn,
+                                                **detect_kwargs)
+        except (ValueError, IndexError):
+            landmarks1 = None
+        if landmarks1 is None:
+            return 0
+        try:
+            landmarks2 = detect_landmarks_batch(gen_img_batch, model, device, mean, std, img_size, mtcnn=mtcnn,
+                                                **detect_kwargs)
+        except (ValueError, IndexError):
+            landmarks2 = None
+        if landmarks2 is None:
+            print("could not detect landmarks")
+            landmarks2 = landmarks1
+        return landmarks_loss_coef * landmarks_loss(landmarks1, landmarks2)
+
+
+class LandmarksTerm:
+    """The landmark regressor, the detector and the distance, loaded once: term(edited, original) -> float."""
+
+    def __init__(self, coef, mobilenet_checkpoint, mtcnn_weights, device):
+        from . import mobilenet_facial, mobilenet_hip, mtcnn_hip
+        from .landmarks_loss import LandmarksLoss
+        sd = None if mobilenet_checkpoint == "synthetic" else mobilenet_facial.load_checkpoint(mobilenet_checkpoint)
+        self.model = mobilenet_hip.build_mobilenet(sd, device=device, input_size=224)
+        self.mtcnn = mtcnn_hip.build_mtcnn(mtcnn_weights, device=device)
+        self.loss, self.coef, self.device = LandmarksLoss(), float(coef), device
+        self.mean, self.std = utils.get_mean_std(device)
+
+    @staticmethod
+    def available(mobilenet_checkpoint, mtcnn_weights):
+        net = mobilenet_checkpoint == "synthetic" or os.path.isfile(mobilenet_checkpoint or "")
+        det = mtcnn_weights == "synthetic" or all(os.path.isfile(os.path.join(mtcnn_weights or "", n + ".npy"))
+                                                  for n in ("pnet", "rnet", "onet"))
+        return net and det
+
+    def __call__(self, img, orig):
+        return float(compute_landmarks_loss(img, orig, self.loss, self.coef, self.model, self.device, self.mean,
+                                            self.std, 224, mtcnn=self.mtcnn))
 
 
 def initial_delta(seed=0, init_std=0.01, device="cpu"):
@@ -509,6 +628,30 @@ class DirectionFinder:
         self.last = {"it": self.it, "batch": self._cur_i, "lr": lr_t, "grad": grad, "parts": buf[-4:]}
         return self.last
 
+    def landmarks_value(self, term):
+        """The landmarks term of the iteration just stepped, written into parts[2] of ``self.last`` for log_line.
+        Forward only, outside the step: the iteration's global batch is rendered again with the direction the step
+        used (styles_direction still holds the pre-update delta until the next local_step writes the new one).  The
+        synthesis is deterministic under the same kernel plan, so on one rank these are the step's images bit for bit.
+        On several ranks the step rendered each rank's shard (planned as the global batch, plan_batch) and this renders
+        the whole batch on the printing rank: the same plan where plan_batch is the global batch size (the default),
+        otherwise the images may differ in their last bits.  The original images are rendered again too (the step's
+        copies live on other streams and, on several ranks, on other devices): one extra forward per printed line.
+        With noise_mode 'random' the noise is drawn from a forked generator state (the run's random stream is left as
+        it was) and differs from the step's."""
+        lo, hi = self._cur_span
+        styles = self.styles_array[lo:hi]
+        d = self.styles_direction[:, self.t_idx]
+        rng_devices = [self.device] if self.device.type == "cuda" else []
+        with torch.no_grad(), torch.random.fork_rng(devices=rng_devices), self._plan(hi - lo):
+            orig = self.synth_fn(self.G, self.until_k, styles, self.temp_shapes, self.noise_mode)
+            img = self._synth_edited(styles, d)
+        value = term(img, orig)
+        parts = self.last["parts"].clone()
+        parts[2] = value
+        self.last["parts"] = parts
+        return value
+
     def log_line(self):
         p = self.last["parts"].tolist()
         g = self.last["grad"].norm().item()
@@ -660,6 +803,10 @@ def _cli():
     @click.option("--text_features", type=str, default=None, help="npz of precomputed text directions ('small'/'large')")
     @click.option("--id_weights", type=str, default="id_loss/model_ir_se50.pth", show_default=True)
     @click.option("--conv_clamp", type=float, default=256.0, help="conv_clamp of a state_dict network (not stored in it)")
+    @click.option("--mobilenet_checkpoint", type=str, default="mobilenet_224_model_best_gdconv_external.pth.tar",
+                  show_default=True, help="MobileNet-GDConv landmark regressor checkpoint, or 'synthetic'")
+    @click.option("--mtcnn_weights", type=str, default="MTCNN/weights", show_default=True,
+                  help="directory with pnet.npy / rnet.npy / onet.npy, or 'synthetic'")
     @click.option("--allow_synthetic_losses", is_flag=True,
                   help="seeded synthetic CLIP / IR-SE50 weights (implied by --network synthetic)")
     @click.option("--impl", type=click.Choice(["hip", "torch"]), default="hip",
@@ -668,12 +815,13 @@ def _cli():
                        clip_loss_type, resolution, batch_size, learning_rate, n_epochs, resume, identity_loss_coef,
                        landmarks_loss_coef, l2_reg_coef, clip_loss_coef, n_seeds, seed, per_gpu_batch, max_iterations,
                        init_std, clip_weights, clip_weights_large, clip_bpe, text_features, id_weights, conv_clamp,
-                       allow_synthetic_losses, impl):
+                       mobilenet_checkpoint, mtcnn_weights, allow_synthetic_losses, impl):
         from .id_loss import IDLoss
         world = _dist.init_from_env(use_cuda=True)
         device = torch.device("cuda", world.device_index)
         torch.cuda.set_device(device)
-        if landmarks_loss_coef != 0:
+        landmarks_on = landmarks_loss_coef != 0 and LandmarksTerm.available(mobilenet_checkpoint, mtcnn_weights)
+        if landmarks_loss_coef != 0 and not landmarks_on:
             warnings.warn("landmarks loss adds no gradient in the reference (no_grad, find_direction.py:90); ignored")
         synthetic_losses = allow_synthetic_losses or network_pkl in (None, "", "synthetic")
         G = load_generator(network_pkl, resolution, device, conv_clamp=conv_clamp)
@@ -701,6 +849,10 @@ def _cli():
         if world.rank == 0:
             print(f"training param shape {tuple(finder.delta.shape)}")
             print(f"Total number of iterations: {finder.total_iterations}")
+        # the landmarks term lives on the printing rank only, and is evaluated only for the lines that rank prints
+        landmarks = None
+        if landmarks_on and world.rank == 0:
+            landmarks = LandmarksTerm(landmarks_loss_coef, mobilenet_checkpoint, mtcnn_weights, device)
         t1 = time.time()
         total = finder.total_iterations if max_iterations is None else min(max_iterations, finder.total_iterations)
         for _ in range(total):
@@ -708,6 +860,8 @@ def _cli():
             if world.rank == 0 and finder.it % 1000 == 999:
                 finder.save(f"{outdir}/direction_last.npz")
             if world.rank == 0 and finder.it % 10 == 0:
+                if landmarks is not None:
+                    finder.landmarks_value(landmarks)
                 print(finder.log_line())
         if world.rank == 0:
             finder.save(f'{outdir}/direction_{text_prompt.replace(" ", "_")}.npz')

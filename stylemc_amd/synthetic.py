@@ -157,6 +157,47 @@ def e4e_state_dict(module, seed=0):
     return out
 
 
+def mobilenet_state_dict(module, seed=0):
+    """seeded_state_dict for the MobileNet-GDConv landmark regressors (mobilenet_facial.py) with the weights of every
+    conv that feeds a ReLU6 (the ``....0.weight`` of a conv + BN + ReLU6 triple) scaled by sqrt(2): with the plain
+    1/fan_in weights each of the 35 rectified layers halves the signal's variance and the 136 outputs are the BatchNorm
+    biases, whatever the image."""
+    out = seeded_state_dict(module, seed=seed)
+    for key, v in out.items():
+        if v.dim() == 4 and key.endswith(".0.weight"):
+            out[key] = v * math.sqrt(2.0)
+    return out
+
+
+def mtcnn_weights(seed=0):
+    """Seeded stand-ins for the MTCNN weight files: {'pnet' | 'rnet' | 'onet': {named_parameters() name: float32
+    array}}.  Conv / FC weights ~ N(0, 2 / fan_in) (He: the PReLU layers keep their scale), biases N(0, 0.02), PReLU
+    slopes 0.25; the box-offset heads (conv4_2 / conv5_2 / conv6_2) and O-Net's landmark head are scaled by 0.1, so
+    calibrated boxes stay near their windows, and the landmark head's bias is 0.5 (points about the box centre).  The
+    class heads keep the He scale: their two logits differ by O(1), so the face probabilities spread over (0, 1) and
+    some windows of any textured image pass the thresholds (a published checkpoint finds nothing in such an image)."""
+    from .MTCNN import get_nets
+    out = {}
+    for name in get_nets.NAMES:
+        net, wts = get_nets.NETS[name](), {}
+        for key, p in net.named_parameters():
+            shape, tag = tuple(p.shape), f"mtcnn.{name}.{key}"
+            if "prelu" in key:
+                t = torch.full(shape, 0.25)
+            elif key.endswith(".weight"):
+                t = _normal(shape, seed, tag, math.sqrt(2.0 / int(np.prod(shape[1:]))))
+            else:
+                t = _normal(shape, seed, tag, 0.02)
+            head = key.split(".")[0]
+            if head in ("conv4_2", "conv5_2", "conv6_2", "conv6_3"):
+                t = t * 0.1
+                if head == "conv6_3" and key.endswith(".bias"):
+                    t = t + 0.5
+            wts[key] = t.numpy().astype(np.float32)
+        out[name] = wts
+    return out
+
+
 def _is_prelu(module, key):
     mod = module
     for part in key.split(".")[:-1]:
